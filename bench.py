@@ -9,7 +9,16 @@ an HBM rate.  Each rank (one process per GPU) processes its own frame-index shar
 batch b goes to rank b % N); there is no collective on the data path, so scaling is weak.
 
 Launched as  python bench.py --gpus N --steps K --warmup W  (torch.distributed.run for N>1).
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run does what the headline needs and no more: it builds the ring, warms up, times the
+K steps and prints ONE JSON line on rank 0 with metric, value, unit, higher_is_better, dtype,
+ms_per_step (wall milliseconds per timed step) and the roofline of those same K launches.
+  --dump-outputs DIR  after the timed steps, write what the last timed step left in its
+                output batch as DIR/<name>.npy (float32 / float64): frame 0 in full, a seeded
+                4 Mi-element sample of the whole batch, and every pixel row's sum.  The inputs are
+                seeded, so two builds run with the same arguments compare output for output.
+  --full        also run the legs below, which take runs of their own (minutes in all), write
+                the full record to the detail file and print the compact headline with a summary
+                of each (a plain run's roofline has neither traffic nor isolated launches):
   roofline      algorithmic bytes per launch / mean per-launch hipEvent duration, vs 8 TB/s;
                 traffic = HBM bytes per launch from rocprofv3 PMC (FETCH_SIZE x 2 per the
                 gfx950 correction in MI355X_MICROARCH.md §HBM, + WRITE_SIZE), rank 0 at N=1
@@ -66,6 +75,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--batch", type=int, default=32, help="frames per step (configs[1]: 32)")
     ap.add_argument("--ring-gb", type=float, default=2.4, help="in+out bytes the steps rotate over")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (PMC traffic, isolated launches, CPU baselines, "
+                         "sizes, configs[4] sweep, end-to-end, JPEG mode, per-frame, distributor); the --no-* "
+                         "options below skip single legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output batch to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="cpu_baseline sample length (0 = skip)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC traffic passes")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host->host end-to-end leg")
@@ -85,6 +100,21 @@ def parse():
     ap.add_argument("--host-copy-child", type=float, default=0.0, help=argparse.SUPPRESS)  # host_copy_ceiling child
     ap.add_argument("--jpeg-child", type=int, default=-1, help=argparse.SUPPRESS)  # jpeg leg on device N
     return ap.parse_args()
+
+
+def is_child(args):
+    """A hidden child mode (one leg's own process): its options are the leg's, as its parent set them."""
+    return bool(args.probe or args.jpeg_child >= 0 or args.cpu_worker or args.host_copy_child)
+
+
+def select_legs(args):
+    """Without --full a bench run (never a leg's child) is plain: the headline's own steps and
+    none of the legs beside them."""
+    if not args.full and not is_child(args):
+        args.no_traffic = args.no_e2e = args.no_jpeg = args.no_distributor = True
+        args.no_sizes = args.no_sweep = args.no_per_frame = True
+        args.cpu_seconds = 0.0
+    return args
 
 
 # ---------------------------------------------------------------------------------------
@@ -115,6 +145,39 @@ def make_ring(ctx, batch, ring_gb, np, rank=0, world=1, hw=(H, W), distinct=97):
         srcs.append(s)
         dsts.append(d)
     return srcs, dsts, batch_bytes, host
+
+
+DUMP_SAMPLE = 1 << 22  # elements of the seeded sample over the whole output batch
+
+
+def last_step_outputs(dsts, steps):
+    """The ring's output buffer that the last of `steps` timed steps wrote: step s (from 0)
+    writes slot s % len(dsts) (vf_bench_device_ring)."""
+    return dsts[(steps - 1) % len(dsts)]
+
+
+def dump_outputs(ctx, dst, batch, batch_bytes, out_dir, np, rank=0):
+    """--dump-outputs: what the timed path left in device buffer `dst`, the output batch of the
+    last timed step (batch x H x W x 3 uint8, what a caller of vf_invert_device receives), as
+      output_frame0.npy    frame 0 in full, float32 [H, W, 3]
+      output_sample.npy    float32 [DUMP_SAMPLE]: the bytes at DUMP_SAMPLE fixed positions of the
+                           whole batch (np.random.default_rng(0), sorted), first and last byte included
+      output_row_sums.npy  float64 [batch, H]: the sum of every pixel row, so each byte counts
+    Ranks above 0 write <name>_rank<r>.npy.  Returns {name: path}."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = np.empty(batch_bytes, np.uint8)
+    ctx.download(host, dst, batch_bytes)
+    ctx.sync()
+    idx = np.sort(np.random.default_rng(0).integers(0, batch_bytes, DUMP_SAMPLE))
+    idx[0], idx[-1] = 0, batch_bytes - 1
+    arrays = {"output_frame0": host[:FRAME_BYTES].reshape(H, W, C).astype(np.float32),
+              "output_sample": host[idx].astype(np.float32),
+              "output_row_sums": host.reshape(batch, H, W * C).sum(axis=2, dtype=np.float64)}
+    paths = {}
+    for name, a in arrays.items():
+        paths[name] = os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy")
+        np.save(paths[name], a)
+    return paths
 
 
 def probe(args):
@@ -836,9 +899,13 @@ def jpeg_child(args):
     print(json.dumps(jpeg), flush=True)
 
 
+def jpeg_child_cmd(device, batch, cpu_seconds):
+    return [sys.executable, os.path.abspath(__file__), "--jpeg-child", str(device), "--batch", str(batch),
+            "--cpu-seconds", str(cpu_seconds)]
+
+
 def run_jpeg_child(device, batch, cpu_seconds, timeout_s=300):
-    cmd = [sys.executable, os.path.abspath(__file__), "--jpeg-child", str(device), "--batch", str(batch),
-           "--cpu-seconds", str(cpu_seconds)]
+    cmd = jpeg_child_cmd(device, batch, cpu_seconds)
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
     except subprocess.TimeoutExpired:
@@ -996,7 +1063,7 @@ def emit(line, path=None):
 
 
 def main():
-    args = parse()
+    args = select_legs(parse())
     if args.probe:
         return probe(args)
     if args.jpeg_child >= 0:
@@ -1065,8 +1132,13 @@ def main():
     region_ms, _ = ctx.bench_device_ring(srcs, dsts, batch_bytes, args.steps)  # returns synchronised
     barrier_sync()
     elapsed = time.perf_counter() - t0
-    # untimed: isolated per-launch durations (event pair around each launch) for reference
-    _, isolated = ctx.bench_device_ring(srcs, dsts, batch_bytes, min(args.steps, 60), per_launch=True)
+    if args.dump_outputs and args.steps > 0:
+        paths = dump_outputs(ctx, last_step_outputs(dsts, args.steps), args.batch, batch_bytes,
+                             args.dump_outputs, np, rank)
+        log(f"rank {rank}: outputs of timed step {args.steps - 1}: {sorted(paths.values())}")
+    isolated = None
+    if args.full:  # untimed: isolated per-launch durations (event pair around each launch) for reference
+        _, isolated = ctx.bench_device_ring(srcs, dsts, batch_bytes, min(args.steps, 60), per_launch=True)
 
     def reduce_max(x):
         if world == 1:
@@ -1185,7 +1257,8 @@ def main():
                          "algorithmic_bytes_per_launch": 2 * batch_bytes,
                          "mean_launch_ms": round(mean_ms, 5),
                          "timing": "hipEvent pair around the K back-to-back launches on their stream / K",
-                         "isolated_launch_ms_median": round(float(np.median(isolated)), 5),
+                         "isolated_launch_ms_median": (None if isolated is None
+                                                       else round(float(np.median(isolated)), 5)),
                          "traffic_detail": traffic_detail},
             "cpu_baseline": cpu,
             "sizes": sizes,
@@ -1195,7 +1268,10 @@ def main():
             "distributor": fanout,
             "per_frame": per_frame,
         }
-        emit(line)
+        if args.full:
+            emit(line)
+        else:  # no legs to keep: the line is the whole record, no detail file
+            print(json.dumps(headline(line)), flush=True)
     if world > 1:
         try:  # the other ranks have left (after the last collective); the line is out already
             dist.destroy_process_group()
