@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/vfilter.h"
+#include "vf_env.h"
 #include "vf_host_mem.h"
 #include "vf_internal.h"
 #include "vf_jpeg_codec.h"
@@ -44,13 +45,7 @@ struct ErrState {
 };
 thread_local ErrState g_thread_err;
 
-size_t env_size(const char *name, size_t dflt) {
-  const char *v = std::getenv(name);
-  if (!v || !*v) return dflt;
-  char *end = nullptr;
-  unsigned long long x = std::strtoull(v, &end, 0);
-  return (end && *end == 0) ? (size_t)x : dflt;
-}
+using vf::env_size;
 
 }  // namespace
 

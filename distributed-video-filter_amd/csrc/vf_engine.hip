@@ -29,6 +29,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "vf_env.h"
 #include "vf_host_mem.h"
 #include "vf_internal.h"
 
@@ -41,14 +42,6 @@ constexpr int kStatusHip = -2;  // VF_E_HIP
 constexpr uint32_t kGateMinShift = 15;
 constexpr size_t kGateFlagBytes = 4096;
 constexpr size_t kGateStatus = 1023;  // index of the status word in the flag page
-
-size_t env_or(const char *name, size_t dflt) {
-  const char *v = std::getenv(name);
-  if (!v || !*v) return dflt;
-  char *end = nullptr;
-  unsigned long long x = std::strtoull(v, &end, 0);
-  return (end && *end == 0) ? (size_t)x : dflt;
-}
 
 bool fired(hipEvent_t e, hipError_t *err) {
   hipError_t q = hipEventQuery(e);
@@ -183,13 +176,13 @@ hipError_t Engine::init(int device, int nslots, size_t slot_bytes, const LaunchC
   device_ = device;
   cfg_ = cfg;
   slot_bytes_ = slot_bytes;
-  pool_.reset(new CopyPool((int)env_or("VF_HOST_THREADS", 8)));
+  pool_.reset(new CopyPool((int)env_size("VF_HOST_THREADS", 8)));
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) {
     *err = std::string("hipSetDevice failed: ") + hipGetErrorString(e);
     return e;
   }
-  zero_copy_ = env_or("VF_ZEROCOPY", 1) != 0;
+  zero_copy_ = env_size("VF_ZEROCOPY", 1) != 0;
   slots_.resize((size_t)nslots);
   for (auto &s : slots_) {
     if ((e = hipEventCreate(&s.h0)) != hipSuccess || (e = hipEventCreate(&s.k0)) != hipSuccess ||
@@ -409,7 +402,7 @@ hipError_t Engine::ensure_staging() {
   (void)hipGetLastError();
   stg_din_ = static_cast<uint8_t *>(di);
   stg_dout_ = static_cast<uint8_t *>(dout);
-  if (!cpool_) cpool_.reset(new CopyPool((int)env_or("VF_HOST_THREADS", 8) + 1, (size_t)256 << 10));
+  if (!cpool_) cpool_.reset(new CopyPool((int)env_size("VF_HOST_THREADS", 8) + 1, (size_t)256 << 10));
   stg_ready_ = true;
   return hipSuccess;
 }
@@ -426,8 +419,8 @@ int Engine::run_gated(const Seg &sg, JobResult *out) {
   // frame takes 0.60-0.66 ms instead of 0.73-0.76 (run_staged copies it whole, then launches 3
   // pieces), within 2-12 % of a page-locked source; at 480p and 1080p the two forms measured
   // within noise of each other (profiles/r06_dropin_gated_ab.txt).
-  const bool enabled = env_or("VF_STAGE_GATED", 1) != 0;
-  const size_t min_len = env_or("VF_STAGE_GATE_MIN", (size_t)8 << 20);
+  const bool enabled = env_size("VF_STAGE_GATED", 1) != 0;
+  const size_t min_len = env_size("VF_STAGE_GATE_MIN", (size_t)8 << 20);
   if (!enabled || sg.len == 0 || sg.len <= min_len || sg.len > kStagedMax || mapped(sg.src, sg.len)) return -1;
   uint8_t *dd = mapped(sg.dst, sg.len);
   const bool stage_out = dd == nullptr;
@@ -472,7 +465,7 @@ int Engine::run_gated(const Seg &sg, JobResult *out) {
   hipError_t e = (a && b) ? hipEventRecord(a, s_map_) : hipErrorOutOfMemory;
   // 100 ms without a piece: the copy stalled (it never waits on the GPU); the kernel gives up.
   // VF_STAGE_GATE_BUDGET_US overrides (tests drive the give-up path with 0).
-  const uint64_t budget_us = env_or("VF_STAGE_GATE_BUDGET_US", 100000);
+  const uint64_t budget_us = env_size("VF_STAGE_GATE_BUDGET_US", 100000);
   const uint64_t budget = clock_khz_ * budget_us / 1000;
   if (e == hipSuccess) {
     gate_gen_ = (gate_gen_ + 1) & 0xFFFFFFu;
@@ -511,7 +504,7 @@ int Engine::run_gated(const Seg &sg, JobResult *out) {
     out->kernel_ms = out->gpu_ms = ms;
     out->zero_copy = true;
     out->timeline.push_back(ChunkTime{sg.len, 0.f, 0.f, ms, ms});
-    if (env_or("VF_STAGE_TRACE", 0) != 0)  // read per call: tests switch it on
+    if (env_size("VF_STAGE_TRACE", 0) != 0)  // read per call: tests switch it on
       std::fprintf(stderr, "vf_stage: gated %zu B, %zu pieces, %d pool workers, GPU %.1f us%s\n", sg.len, np, cpool_->workers(),
                    ms * 1000.f, gave_up ? ", re-run ungated after a give-up" : "");
   }
@@ -549,7 +542,7 @@ bool Engine::run_staged(const std::vector<Seg> &segs, size_t total, JobResult *o
   // extra launch over PCIe costs more than the overlap gains, so a frame up to 8 MiB is one
   // piece (1080p: 0.223 ms per call at 1 piece, 0.235 at 2, 0.240 at 3, 0.267 at 6;
   // profiles/r03_per_frame_pieces.txt); larger jobs take 3.  VF_STAGE_PIECES overrides.
-  static const size_t kPieces = env_or("VF_STAGE_PIECES", 0);
+  static const size_t kPieces = env_size("VF_STAGE_PIECES", 0);
   const size_t npieces = kPieces ? kPieces : total <= ((size_t)8 << 20) ? 1 : 3;
   const size_t piece = std::max<size_t>((size_t)256 << 10, (total / npieces + 65535) & ~(size_t)65535);
   std::vector<P> ps;
@@ -580,7 +573,7 @@ bool Engine::run_staged(const std::vector<Seg> &segs, size_t total, JobResult *o
       }
     });
   const int nw = cpool_->workers();
-  static const bool trace = env_or("VF_STAGE_TRACE", 0) != 0;  // per-call host timeline on stderr
+  static const bool trace = env_size("VF_STAGE_TRACE", 0) != 0;  // per-call host timeline on stderr
   const auto t0 = std::chrono::steady_clock::now();
   auto us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
   std::vector<double> tl;

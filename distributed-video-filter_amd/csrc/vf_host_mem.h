@@ -22,6 +22,8 @@
 #include <map>
 #include <mutex>
 
+#include "vf_env.h"
+
 namespace vf {
 
 inline int device_numa_node(int device) {
@@ -60,10 +62,7 @@ struct PinnedRegistry {
 inline hipError_t numa_pinned_alloc(void **out, size_t n, int node) {
   *out = nullptr;
   if (n == 0) n = 1;
-  static const bool enabled = [] {
-    const char *v = std::getenv("VF_NUMA");
-    return !(v && v[0] == '0');
-  }();
+  static const bool enabled = env_on("VF_NUMA");
 #if defined(__x86_64__) && defined(SYS_mbind)
   if (enabled && node >= 0 && node < 1024) {
     const size_t len = (n + 4095) & ~(size_t)4095;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "vf_jpeg.h"
+#include "vf_jpeg_plan.h"
 
 namespace vf {
 namespace jpeg {
@@ -132,11 +133,15 @@ class Codec {
 
  private:
   int init(std::string *err);
-  int prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int n, int flags, std::string *err);
+  int prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int n, int flags, const JpegSwitches &sw,
+                     bool invert, std::string *err);  // parse, layout, uploads; resolves plan_
   int run_decode(int bgr, bool invert, std::string *err);
   int run_decode_post(int bgr, bool invert, std::string *err);  // write, DC, IDCT, colour
+  hipError_t span_pass(int p);
   int finish_sync(std::string *err);  // host-looped span passes after the queued ones
   int check_decode(std::string *err);
+  template <class Tail>  // the one resync loop: check, finish_sync, run_decode_post, tail, check again
+  int settle_decode(int bgr, bool invert, Tail &&tail, std::string *err);
   int prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs, int n, int quality, int subsamp,
                      bool fastdct, std::string *err);
   int run_encode(int bgr, bool fastdct, std::string *err);
@@ -167,9 +172,6 @@ class Codec {
   int dmax_w_ = 0, dmax_h_ = 0;
   uint64_t dblocks_ = 0, dpix_bytes_ = 0;
   uint32_t dmax_wg_ = 0;       // speculative sync: workgroups of the largest segment
-  bool spec_ok_ = true;        // every frame fits the speculative resolver
-  bool tabs4_ = true;          // every frame fits the span sync's 4-table layout (DecFrame::tabs4)
-  bool pow2bpm_ = true;        // every frame's blocks per MCU divide 16 (the syncs' LSB-first lanes)
   uint64_t spec_calls_ = 0, spec_fallbacks_ = 0;
   DevBuf d_tE_, d_tX_, d_tXc_, d_pX_, d_pC_, d_wF_, d_rE_, d_rK_, d_qX_, d_qC_, d_rL_,
       d_unres_;
@@ -183,12 +185,8 @@ class Codec {
   int esub_ = 1;  // TJSAMP_* of the prepared encode
   uint32_t emax_blocks_ = 0, emax_tiles_ = 0;
   uint64_t eblocks_ = 0, ebits_bytes_ = 0;
-  DevBuf d_eplanes_;  // the invert path's encoder sample planes (fuse_)
-  bool fuse_ = false;
+  DevBuf d_eplanes_;  // the invert path's encoder sample planes (plan_.fuse)
   int dcm_ = -1;  // k_color layout shared by the batch's frames (1..3, 0 general), -1 mixed
-  bool d422_ = false;  // every frame of the batch is standard 4:2:2 (the fused IDCT + colour pass)
-  uint64_t dbits_per_block_ = 0;  // the batch's entropy-coded bits per block (span-sync warm-up)
-  uint32_t sync_warm() const;
   DevBuf d_efr_, d_etab_, d_hdr_, d_esegs_, d_etsum_, d_etotals_, d_dcq_, d_acbits_, d_acscr_, d_bits_, d_pre_, d_bitoff_, d_stream_, d_ffcnt_,
       d_outsize_, d_pack_;
 
@@ -201,12 +199,11 @@ class Codec {
   std::vector<uint64_t> out_sizes_, out_offs_;
   bool spec_check_ = false;           // run_decode queued that flag's read; check_decode tests it
   bool pass_check_ = false;           // the same for the last queued sync pass's change flag
-  int sync_g_ = 4;                    // span width of the queued passes (finish_sync continues them)
-  int sync_t4_ = 0;                   // and their table layout (DecFrame::tabs4)
-  int queued_ = kQueuedPasses;        // span passes queued by run_decode
-  bool sync_spec_ = false;            // run_decode took the speculative sync (the write pass's form)
-  int sync_last_ = 0;                 // exit / count slot of the pass-based sync's result
-  bool enc_fast_ = false;             // submit_invert's DCT (wait_invert re-encodes after finish_sync)
+  // The batch's variant choices, resolved once at the end of prepare_decode from the entry call's
+  // switches; run_decode, finish_sync, run_decode_post and run_encode read nothing else, so a
+  // batch resynchronised at wait_invert continues in the form submit_invert queued.
+  DecodePlan plan_;
+  int sync_slot_ = 0;                 // run state: exit / count slot of the sync's result
   // output bytes per input byte of the codec's last invert batch (0: none yet): the next batch's
   // first D2H copy is sized from it instead of from the input sizes alone (VF_JPEG_FETCH_LEARN=0:
   // the fixed rule), so content that shrinks when re-encoded does not drag twice its output over PCIe

@@ -23,6 +23,7 @@
 #include "vf_jpeg.h"
 #include "vf_jpeg_codec.h"
 #include "vf_jpeg_parse.h"
+#include "vf_jpeg_plan.h"
 
 namespace vf {
 namespace jpeg {
@@ -267,28 +268,9 @@ int Codec::init(std::string *err) {
 }
 
 // Host parse of every frame + batch layout + upload of inputs and descriptors.
-// The invert path's fused colour pass (k_color writes the encoder's sample planes, k_fdct reads
-// them); VF_JPEG_FUSE=0 keeps the pixel round trip (read per call: tests switch it).
-// Bits a span-sync thread decodes before its span in pass 0, so that its entry is (usually)
-// synchronised already: 12 blocks' worth of the batch's bits per block -- the full state (bit
-// position, zigzag index, block-in-MCU) resynchronises at block boundaries (hard 1080p: ~250
-// bits per block, 3,008 bits of warm-up; 4K scenes: ~20, 240).  12 rather than 8 blocks: hard
-// 1080p sync 4-9 % shorter on each of four content seeds, 4K scenes unchanged
-// (profiles/r05_jpeg_sync_warm_ab.txt).  VF_JPEG_SYNC_WARM=<bits> overrides (0: guessed
-// entries), read per call: tests and A/Bs switch it inside one process.
-uint32_t Codec::sync_warm() const {
-  const char *v = std::getenv("VF_JPEG_SYNC_WARM");
-  if (v && *v && std::strcmp(v, "auto") != 0) return (uint32_t)std::strtoul(v, nullptr, 10);
-  return (uint32_t)std::min<uint64_t>(4096, 12 * dbits_per_block_) & ~31u;
-}
-
-static bool fuse_enabled() {
-  const char *v = std::getenv("VF_JPEG_FUSE");
-  return !(v && std::strcmp(v, "0") == 0);
-}
-
-int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int n, int flags, std::string *err) {
-  fuse_ = false;
+// Ends with the batch's plan (vf_jpeg_plan.h), resolved from the entry call's switches.
+int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int n, int flags, const JpegSwitches &sw,
+                          bool invert, std::string *err) {
   if (n <= 0) {
     *err = "empty batch";
     return kInvalid;
@@ -303,7 +285,7 @@ int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int 
   uint32_t tiles = 0, subs = 0, wgs = 0;
   uint64_t trs = 0;
   dmax_tiles_ = dmax_sub_ = dmax_blocks_ = dmax_wg_ = 0;
-  spec_ok_ = true;
+  BatchTraits traits;  // all true until a frame says otherwise
   dmax_w_ = dmax_h_ = 0;
   // per frame, in parallel: markers, scan end, geometry and decode tables
   std::vector<std::string> ferr((size_t)n);
@@ -365,11 +347,7 @@ int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int 
   dsg_.clear();
   dcm_ = -2;  // the batch's common k_color layout, or -1 (mixed)
   // VF_JPEG_IDCT24=0: every frame on the 32-bit column pass (an A/B and test selector)
-  const char *i24 = std::getenv("VF_JPEG_IDCT24");
-  const bool idct24 = !(i24 && std::strcmp(i24, "0") == 0);
-  d422_ = true;  // every frame standard 4:2:2 (k_idct_color422)
-  tabs4_ = true;  // every frame fits the span sync's 4-table layout (DecFrame::tabs4)
-  pow2bpm_ = true;  // every frame's blocks per MCU divide 16 (the span and speculative syncs' LSB-first lanes)
+  const bool idct24 = flag_on(sw.idct24);
   for (int f = 0; f < n; ++f) {
     const Parsed &P = parsed[(size_t)f];
     DecFrame &F = dfr_[(size_t)f];
@@ -382,7 +360,7 @@ int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int 
       F.flags |= cm << 1;
       if (idct24 && m24ok[(size_t)f]) F.flags |= kDecIdct24;
       dcm_ = dcm_ == -2 || dcm_ == (int)cm ? (int)cm : -1;
-      d422_ = d422_ && g.ncomp == 3 && g.hs[0] == 2 && g.vs[0] == 1 && g.hs[1] == 1 && g.vs[1] == 1 &&
+      traits.d422 = traits.d422 && g.ncomp == 3 && g.hs[0] == 2 && g.vs[0] == 1 && g.hs[1] == 1 && g.vs[1] == 1 &&
               g.hs[2] == 1 && g.vs[2] == 1 && g.bpm == 4;
     }
     {  // the span sync's 4-table layout: components with the same (DC, AC) table ids share a
@@ -403,8 +381,8 @@ int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int 
       }
       if (ok && nsl == 1) rep |= (rep & 0x300u) << 2;  // slot 1 unused: a copy of slot 0
       F.tabs4 = ok ? (s4 | rep | 0x80000000u) : 0u;
-      tabs4_ = tabs4_ && ok;
-      pow2bpm_ = pow2bpm_ && F.g.bpm >= 1 && F.g.bpm <= 16 && (F.g.bpm & (F.g.bpm - 1)) == 0;
+      traits.tabs4 = traits.tabs4 && ok;
+      traits.pow2bpm = traits.pow2bpm && F.g.bpm >= 1 && F.g.bpm <= 16 && (F.g.bpm & (F.g.bpm - 1)) == 0;
     }
     F.blk0 = blk;
     for (int c = 0; c < P.ncomp; ++c) {
@@ -445,7 +423,7 @@ int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int 
         trs += (uint64_t)S.nwg * 256;
         dmax_wg_ = std::max(dmax_wg_, S.nwg);
         // k_resolve stages at most 4096 workgroups and 16384 (workgroup, entry) transitions per segment
-        if (S.nwg > 4096 || (uint64_t)S.nwg * (uint64_t)F.g.bpm > 16384) spec_ok_ = false;
+        if (S.nwg > 4096 || (uint64_t)S.nwg * (uint64_t)F.g.bpm > 16384) traits.spec_ok = false;
       }
       S.us_off = us_off;
       in_off += align_up(len, 16);
@@ -477,7 +455,7 @@ int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int 
   {
     uint64_t bits = 0;
     for (const DecSeg &S : dsg_) bits += (uint64_t)S.in_len * 8;
-    dbits_per_block_ = blk ? bits / blk : 0;
+    traits.bits_per_block = blk ? bits / blk : 0;
   }
   // scan segments: [0, nseg) unstuff tiles, [nseg, 2 nseg) subsequence counts, then DC sequences
   // (per entropy-coded segment and component: restart intervals reset the DC prediction)
@@ -569,6 +547,9 @@ int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int 
     prep_ms_[1] = ms(tp1, tp2);
     prep_ms_[2] = ms(tp2, clk::now());
   }
+  traits.max_sub = dmax_sub_;
+  plan_ = resolve(sw, traits, invert);
+  plan_.enc_fast = (flags & kFlagFastDct) != 0;
   return kOk;
 }
 
@@ -587,46 +568,27 @@ int Codec::run_decode(int bgr, bool invert, std::string *err) {
   CK(dec_unstuff_write(sg, ns, dmax_tiles_, d_in_.as<uint8_t>(), d_tile_.as<uint32_t>(), us_len,
                        d_us_.as<uint8_t>(), s_));
   CK(stage_event(1));
-  // 2. synchronise the subsequence entry states: speculative (one pass, one flag read), with
-  // the pass-based sync as the fallback when a link did not rejoin (VF_JPEG_SYNC=pass forces it)
-  // VF_JPEG_SYNC = spec | pass | auto (default).  auto: speculative for frames of up to
-  // kSpecAutoSubs subsequences (measured, MI355X, q85 4:2:2 batches of 32: 480p 50.4k vs 37.6k
-  // fps, 1080p 18.0k vs 17.2k; 4K 5.48k vs 5.65k, where the bpm-fold trajectory decode costs
-  // more than the pass chains it removes).
-  const int mode = [] {  // read per call: tests switch it inside one process
-    const char *v = std::getenv("VF_JPEG_SYNC");
-    if (v && std::strcmp(v, "pass") == 0) return 1;
-    if (v && std::strcmp(v, "spec") == 0) return 2;
-    return 0;
-  }();
-  // the LSB-first lanes (SpanLaneRT) when every frame's block cycle divides 16 (k_spec's
-  // 2-bit component slots; k_syncg's 1-bit table slots need it to divide 32); VF_JPEG_SYNC_LSB=0: off
-  const bool lsb = pow2bpm_ && [] {  // read per call: tests switch it inside one process
-    const char *v = std::getenv("VF_JPEG_SYNC_LSB");
-    return !(v && std::strcmp(v, "0") == 0);
-  }();
-  constexpr uint32_t kSpecAutoSubs = 12288;
-  const bool use_spec = spec_ok_ && (mode == 2 || (mode == 0 && dmax_sub_ <= kSpecAutoSubs));
-  int pass = 0, last = 0;
-  uint32_t flag = 1;
-  if (use_spec) {
+  // 2. synchronise the subsequence entry states, by the path the plan chose (resolve(),
+  // vf_jpeg_plan.h): speculative (one pass, one flag read), queued span passes, or k_sync
+  const DecodePlan &pl = plan_;
+  int pass = 0;
+  sync_slot_ = 0;  // the span and speculative syncs leave exits / counts in slot 0
+  if (pl.spec) {
     SpecBufs sb{d_tE_.as<uint64_t>(),  d_tX_.as<uint64_t>(), d_tXc_.as<uint32_t>(),
                 d_pX_.as<uint64_t>(),  d_pC_.as<uint32_t>(), d_wF_.as<uint8_t>(),  d_rE_.as<uint8_t>(),
                 d_rK_.as<uint32_t>(),  d_qX_.as<uint64_t>(), d_qC_.as<uint32_t>(), d_rL_.as<uint8_t>(),
                 d_unres_.as<uint32_t>()};
     // k_resolve reports a frame unresolved only when it has more workgroups than it stages,
-    // which prepare_decode already excludes (spec_ok_), so the rest is queued without a host
-    // round trip; check_decode reads the flags after its synchronisation and turns one into an
+    // which prepare_decode already excludes (BatchTraits::spec_ok), so the rest is queued without
+    // a host round trip; check_decode reads the flags after its synchronisation and turns one into an
     // error.  Each segment's k_resolve workgroup stores its flag (0 or 1) straight into the
     // codec's page-locked h_unres_ through the mapping: no fill and no download on the stream.
-    const bool stats = std::getenv("VF_JPEG_SYNC_STATS") != nullptr;
-    if (stats) CK(hipMemsetAsync(d_unres_.p, 0, sizeof(uint32_t) * 16, s_));  // SpecBufs::stats
+    if (pl.stats) CK(hipMemsetAsync(d_unres_.p, 0, sizeof(uint32_t) * 16, s_));  // SpecBufs::stats
     CK(dec_sync_spec(sg, fr, ns, dmax_wg_, d_us_.as<uint8_t>(), us_len, sb, d_exit_[0].as<uint64_t>(),
-                     d_cnt_[0].as<uint32_t>(), static_cast<uint32_t *>(unres_dev_), lsb ? 1 : 0, s_));
+                     d_cnt_[0].as<uint32_t>(), static_cast<uint32_t *>(unres_dev_), pl.lsb ? 1 : 0, s_));
     spec_check_ = true;
-    flag = 0;  // exits / counts are in slot 0
     ++spec_calls_;
-    if (stats) {
+    if (pl.stats) {
       uint32_t st[16];
       CK(hipStreamSynchronize(s_));  // the codec's stream is non-blocking: the copy below would not wait
       CK(hipMemcpy(st, d_unres_.p, sizeof st, hipMemcpyDeviceToHost));
@@ -641,64 +603,41 @@ int Codec::run_decode(int bgr, bool invert, std::string *err) {
       std::fprintf(stderr, "[vf_jpeg] spec: unresolved %u; walk columns ended explicit %u, their traces joined in one "
                    "subsequence %u, serial traces %u (segments %d)\n", st[0], st[11], st[12], st[13], ns);
     }
-  }
-  // pass-based: spans of G subsequences per thread (VF_JPEG_SYNC_G = 1, 2, 4, 8; 0 = the
-  // host-looped one-subsequence k_sync), kQueuedPasses passes queued without a host round trip
-  // (a pass after convergence returns at once); the last pass's flag is read at check_decode
-  // With every frame on 4 table slots (DecFrame::tabs4; VF_JPEG_SYNC_TABS4=0 turns it off) the
-  // span sync's LDS leaves room for G = 5 at 3 workgroups per CU: 25 % more stream resident.
-  const bool t4 = tabs4_ && [] {
-    const char *v = std::getenv("VF_JPEG_SYNC_TABS4");
-    return !(v && std::strcmp(v, "0") == 0);
-  }();
-  const int sync_g = [t4] {  // read per call: tests switch it inside one process
-    const char *v = std::getenv("VF_JPEG_SYNC_G");
-    const int g = v ? std::atoi(v) : t4 ? 5 : 4;
-    if (g == 5) return t4 ? 5 : 4;
-    return g >= 0 && g <= 4 ? g : g == 8 ? 8 : 4;
-  }();
-
-  const int g_t4 = t4 && (sync_g == 4 || sync_g == 5) ? (lsb ? 2 : 1) : 0;
-  if (flag && sync_g > 0) {
-    // VF_JPEG_SYNC_QUEUED = 1..kQueuedPasses (tests): fewer queued passes, so check_decode
-    // reports them unconverged and finish_sync runs the rest
-    const char *qv = std::getenv("VF_JPEG_SYNC_QUEUED");
-    queued_ = qv ? std::min(std::max(std::atoi(qv), 1), kQueuedPasses) : kQueuedPasses;
+  } else if (pl.g > 0) {
+    // span passes, pl.queued of them queued without a host round trip (a pass after convergence
+    // returns at once); the last pass's flag is read at check_decode
     CK(hipMemsetAsync(d_changed_.p, 0, sizeof(uint32_t) * kMaxPasses, s_));
-    for (int p = 0; p < queued_; ++p)
-      CK(dec_syncg(sync_g, sg, fr, ns, dmax_sub_, d_us_.as<uint8_t>(), us_len, d_exit_[0].as<uint64_t>(),
-                   d_cnt_[0].as<uint32_t>(), d_used_.as<uint64_t>(), d_ck_.as<uint64_t>(), d_ckrem_.as<uint32_t>(),
-                   d_changed_.as<uint32_t>(), p, sync_warm(), g_t4, s_));
+    for (int p = 0; p < pl.queued; ++p) CK(span_pass(p));
     CK(h_flag_.ensure(64));
-    CK(hipMemcpyAsync(h_flag_.p, d_changed_.as<uint32_t>() + queued_ - 1, sizeof(uint32_t),
+    CK(hipMemcpyAsync(h_flag_.p, d_changed_.as<uint32_t>() + pl.queued - 1, sizeof(uint32_t),
                       hipMemcpyDeviceToHost, s_));
     pass_check_ = true;
-    flag = 0;
-    last = 0;
-    pass = queued_;
-  }
-  if (flag) CK(hipMemsetAsync(d_changed_.p, 0, sizeof(uint32_t) * kMaxPasses, s_));
-  for (; flag;) {
-    const int a = pass & 1;
-    CK(dec_sync(sg, fr, ns, dmax_sub_, d_us_.as<uint8_t>(), us_len, d_exit_[a ^ 1].as<uint64_t>(),
-                d_exit_[a].as<uint64_t>(), d_cnt_[a ^ 1].as<uint32_t>(), d_cnt_[a].as<uint32_t>(),
-                d_used_.as<uint64_t>(), d_ck_.as<uint64_t>(), d_ckrem_.as<uint32_t>(),
-                d_changed_.as<uint32_t>() + (pass % kMaxPasses), pass > 0 ? 1 : 0, s_));
-    last = a;
-    ++pass;
-    if (pass < 2) continue;  // passes 0 and 1 are queued without a host round trip
-    CK(hipMemcpyAsync(&flag, d_changed_.as<uint32_t>() + ((pass - 1) % kMaxPasses), sizeof flag,
-                      hipMemcpyDeviceToHost, s_));
-    CK(hipStreamSynchronize(s_));
-    if (!flag) break;
-    CK(hipMemsetAsync(d_changed_.as<uint32_t>() + (pass % kMaxPasses), 0, sizeof(uint32_t), s_));
-    if (pass > (int)dmax_sub_ + 2) {
-      *err = "Huffman synchronisation did not converge (corrupt stream?)";
-      return kJpeg;
+    pass = pl.queued;
+  } else {
+    // the one-subsequence k_sync, looped by the host with a flag read per pass after the first two
+    CK(hipMemsetAsync(d_changed_.p, 0, sizeof(uint32_t) * kMaxPasses, s_));
+    for (uint32_t flag = 1; flag;) {
+      const int a = pass & 1;
+      CK(dec_sync(sg, fr, ns, dmax_sub_, d_us_.as<uint8_t>(), us_len, d_exit_[a ^ 1].as<uint64_t>(),
+                  d_exit_[a].as<uint64_t>(), d_cnt_[a ^ 1].as<uint32_t>(), d_cnt_[a].as<uint32_t>(),
+                  d_used_.as<uint64_t>(), d_ck_.as<uint64_t>(), d_ckrem_.as<uint32_t>(),
+                  d_changed_.as<uint32_t>() + (pass % kMaxPasses), pass > 0 ? 1 : 0, s_));
+      sync_slot_ = a;
+      ++pass;
+      if (pass < 2) continue;  // passes 0 and 1 are queued without a host round trip
+      CK(hipMemcpyAsync(&flag, d_changed_.as<uint32_t>() + ((pass - 1) % kMaxPasses), sizeof flag,
+                        hipMemcpyDeviceToHost, s_));
+      CK(hipStreamSynchronize(s_));
+      if (!flag) break;
+      CK(hipMemsetAsync(d_changed_.as<uint32_t>() + (pass % kMaxPasses), 0, sizeof(uint32_t), s_));
+      if (pass > (int)dmax_sub_ + 2) {
+        *err = "Huffman synchronisation did not converge (corrupt stream?)";
+        return kJpeg;
+      }
     }
   }
   sync_passes_ = pass;
-  if (std::getenv("VF_JPEG_SYNC_STATS")) {
+  if (pl.stats) {
     uint32_t st[4];
     CK(hipMemcpy(st, d_changed_.as<uint32_t>() + kMaxPasses - 4, sizeof st, hipMemcpyDeviceToHost));
     std::fprintf(stderr,
@@ -708,11 +647,15 @@ int Codec::run_decode(int bgr, bool invert, std::string *err) {
                  (dmax_sub_ + 255) / 256 * (uint32_t)ns);
   }
   CK(stage_event(2));
-  sync_spec_ = use_spec;
-  sync_last_ = last;
-  sync_g_ = sync_g;
-  sync_t4_ = g_t4;
   return run_decode_post(bgr, invert, err);
+}
+
+// Span pass p of the plan's width and table layout, on the batch's unstuffed segments.
+hipError_t Codec::span_pass(int p) {
+  return dec_syncg(plan_.g, d_dsg_.as<DecSeg>(), d_dfr_.as<DecFrame>(), dnseg_, dmax_sub_, d_us_.as<uint8_t>(),
+                   d_totals_.as<uint32_t>(), d_exit_[0].as<uint64_t>(), d_cnt_[0].as<uint32_t>(), d_used_.as<uint64_t>(),
+                   d_ck_.as<uint64_t>(), d_ckrem_.as<uint32_t>(), d_changed_.as<uint32_t>(), p, plan_.warm, plan_.tabs,
+                   s_);
 }
 
 // The queued span passes left a workgroup's last exit changing (a stream that takes more than
@@ -720,17 +663,12 @@ int Codec::run_decode(int bgr, bool invert, std::string *err) {
 // data in practice): more passes, each followed by a flag read, until none changes.  The caller
 // then queues the stages after the sync again.
 int Codec::finish_sync(std::string *err) {
-  const DecFrame *fr = d_dfr_.as<DecFrame>();
-  const DecSeg *sg = d_dsg_.as<DecSeg>();
-  const uint32_t *us_len = d_totals_.as<uint32_t>();
-  for (int p = queued_;; ++p) {
+  for (int p = plan_.queued;; ++p) {
     if (p >= kMaxPasses) {
       *err = "Huffman synchronisation did not converge (corrupt stream?)";
       return kJpeg;
     }
-    CK(dec_syncg(sync_g_, sg, fr, dnseg_, dmax_sub_, d_us_.as<uint8_t>(), us_len, d_exit_[0].as<uint64_t>(),
-                 d_cnt_[0].as<uint32_t>(), d_used_.as<uint64_t>(), d_ck_.as<uint64_t>(), d_ckrem_.as<uint32_t>(),
-                 d_changed_.as<uint32_t>(), p, sync_warm(), sync_t4_, s_));
+    CK(span_pass(p));
     uint32_t flag = 0;
     CK(hipMemcpyAsync(&flag, d_changed_.as<uint32_t>() + p, sizeof flag, hipMemcpyDeviceToHost, s_));
     CK(hipStreamSynchronize(s_));
@@ -746,36 +684,18 @@ int Codec::run_decode_post(int bgr, bool invert, std::string *err) {
   const ScanSeg *segs = d_segs_.as<ScanSeg>();
   const int n = dn_, ns = dnseg_;
   const uint32_t *us_len = d_totals_.as<uint32_t>();
-  const bool use_spec = sync_spec_;
-  const int last = sync_last_;
+  const DecodePlan &pl = plan_;
+  const int last = sync_slot_;
   // 3. block offsets of the subsequences, then the write pass
   // the segments' decoded block counts go straight to the page-locked h_dtot_ (check_decode)
   uint32_t *blocks_total = static_cast<uint32_t *>(dtot_dev_);
   CK(scan_u32(segs + ns, ns, (dmax_sub_ + kScanTile - 1) / kScanTile, d_cnt_[last].as<uint32_t>(),
               d_bstart_.as<uint32_t>(), d_tsum_.as<uint32_t>(), blocks_total, false, s_));
-  // The write pass stores whole 16-B coefficient rows with a per-block mask of the rows stored,
-  // which the IDCT reads: no clear of the coefficient buffer (134 MB per 1080p batch, 1.06 GB
-  // per 4K one).  After the speculative sync always (k_write + clear 118 -> 105 us at 1080p).
-  // After the pass-based sync only when blocks are short: its write pass runs 4 lanes per
-  // subsequence, each of which decodes on to its last block's end and skips its first, which
-  // costs a block per lane -- on hard content (~500 bits per block) k_write4 342 -> 1227 us,
-  // on 4K scenes (~22 bits per block) huffman_write 0.50 -> 0.29 ms, resident 11.1 -> 12.0 k fps
-  // (profiles/r04_jpeg_fuse_chunks_warm_ab.txt, r04_jpeg_chunks_4k_ab.txt).  VF_JPEG_CHUNKS=0 / 1
-  // forces either form.
-  constexpr uint64_t kChunkBitsPerBlock = 128;
-  const bool chunks = [use_spec, this] {  // read per call: tests switch it inside one process
-    const char *v = std::getenv("VF_JPEG_CHUNKS");
-    return v && *v ? std::strcmp(v, "0") != 0 : use_spec || dbits_per_block_ <= kChunkBitsPerBlock;
-  }();
-  uint8_t *const nmask = chunks ? d_nmask_.as<uint8_t>() : nullptr;
-  if (!chunks) CK(hipMemsetAsync(d_coef_.p, 0, dblocks_ * 128, s_));
-  // after the pass-based sync, every subsequence's checkpoints are states of the true path: the
-  // write pass runs 4 lanes per subsequence from them (VF_JPEG_WRITE4=0: one lane)
-  const bool write4 = [] {  // read per call: tests switch it inside one process
-    const char *v = std::getenv("VF_JPEG_WRITE4");
-    return !(v && std::strcmp(v, "0") == 0);
-  }();
-  if (!use_spec && write4)
+  // chunked: whole 16-B coefficient rows + a per-block mask of the rows stored, which the IDCT
+  // reads; else 2-byte scatters into a cleared buffer
+  uint8_t *const nmask = pl.chunks ? d_nmask_.as<uint8_t>() : nullptr;
+  if (!pl.chunks) CK(hipMemsetAsync(d_coef_.p, 0, dblocks_ * 128, s_));
+  if (!pl.spec && pl.write4)
     CK(dec_write4(sg, fr, ns, dmax_sub_, d_us_.as<uint8_t>(), us_len, d_exit_[last].as<uint64_t>(),
                   d_cnt_[last].as<uint32_t>(), d_ck_.as<uint64_t>(), d_ckrem_.as<uint32_t>(),
                   d_bstart_.as<uint32_t>(), d_coef_.as<int16_t>(), d_dcseq_.as<int32_t>(), nmask, s_));
@@ -787,12 +707,8 @@ int Codec::run_decode_post(int bgr, bool invert, std::string *err) {
   CK(scan_i32(segs + 2 * ns, ndcseg_, dc_max_tiles_, d_dcseq_.as<int32_t>(), d_dcpred_.as<int32_t>(),
               d_tsum_.as<int32_t>(), nullptr, true, s_));
   // 5. IDCT, 6. upsample + colour (+ invert).  The invert path on standard 4:2:2 frames does both
-  // in one pass with the decoder planes in LDS (k_idct_color422; VF_JPEG_FUSE_IDCT=0: two passes)
-  const bool fuse_idct = fuse_ && d422_ && [] {  // read per call: tests switch it inside one process
-    const char *v = std::getenv("VF_JPEG_FUSE_IDCT");
-    return !(v && std::strcmp(v, "0") == 0);
-  }();
-  if (fuse_idct) {
+  // in one pass with the decoder planes in LDS (k_idct_color422)
+  if (pl.fuse_idct) {
     CK(stage_event(4));  // the DC scan above is the dc_idct stage; the fused pass the colour stage
     CK(dec_idct_color422(fr, n, dmax_w_, dmax_h_, d_coef_.as<int16_t>(), d_dcpred_.as<int32_t>(), nmask,
                          d_eplanes_.as<uint8_t>(), d_efr_.as<EncFrame>(), invert ? 1 : 0, kSampV[esub_] == 1 ? 1 : 0,
@@ -802,9 +718,9 @@ int Codec::run_decode_post(int bgr, bool invert, std::string *err) {
   }
   CK(dec_idct(fr, n, dmax_blocks_, d_coef_.as<int16_t>(), d_dcpred_.as<int32_t>(), nmask, d_planes_.as<uint8_t>(), s_));
   CK(stage_event(4));
-  // the invert path (fuse_): the encoder's sample planes instead of pixels (enc_sample_rows)
-  CK(dec_color(fr, n, dmax_w_, dmax_h_, d_planes_.as<uint8_t>(), fuse_ ? d_eplanes_.as<uint8_t>() : d_pix_.as<uint8_t>(),
-               bgr, invert ? 1 : 0, fuse_ ? d_efr_.as<EncFrame>() : nullptr, dcm_, s_));
+  // the invert path (pl.fuse): the encoder's sample planes instead of pixels (enc_sample_rows)
+  CK(dec_color(fr, n, dmax_w_, dmax_h_, d_planes_.as<uint8_t>(), pl.fuse ? d_eplanes_.as<uint8_t>() : d_pix_.as<uint8_t>(),
+               bgr, invert ? 1 : 0, pl.fuse ? d_efr_.as<EncFrame>() : nullptr, dcm_, s_));
   CK(stage_event(5));
   return kOk;
 }
@@ -847,7 +763,6 @@ int Codec::prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs
     *err = "unsupported subsampling (TJSAMP_444, 422, 420, GRAY, 440)";
     return kInvalid;
   }
-  fuse_ = false;  // the invert paths turn it on after both prepares
   // Everything below depends only on the frames' sizes and layout and the settings: a batch shaped
   // like this codec's previous one (a worker's steady state) reuses its descriptors, tables,
   // headers and buffers, already on the device (nothing else writes them).
@@ -959,10 +874,11 @@ int Codec::run_encode(int bgr, bool fastdct, std::string *err) {
   const EncTables *tab = d_etab_.as<EncTables>();
   const ScanSeg *segs = d_esegs_.as<ScanSeg>();
   const int n = en_;
+  const bool fuse = plan_.fuse;  // the decoder's colour pass wrote the sample planes
   CK(stage_event(6));
-  CK(enc_fdct(fr, n, emax_blocks_, tab, fuse_ ? d_eplanes_.as<uint8_t>() : d_pix_.as<uint8_t>(), d_dcq_.as<int16_t>(),
+  CK(enc_fdct(fr, n, emax_blocks_, tab, fuse ? d_eplanes_.as<uint8_t>() : d_pix_.as<uint8_t>(), d_dcq_.as<int16_t>(),
               d_acbits_.as<uint32_t>(), d_acscr_.as<uint32_t>(), bgr, fastdct ? 1 : 0, kSampH[esub_], kSampV[esub_],
-              fuse_ ? 1 : 0, s_));
+              fuse ? 1 : 0, s_));
   CK(enc_len(fr, n, emax_blocks_, tab, d_dcq_.as<int16_t>(), d_acbits_.as<uint32_t>(), d_bits_.as<uint32_t>(),
              d_pre_.as<uint32_t>(), s_));
   uint32_t *total_bits = d_etotals_.as<uint32_t>();
@@ -1027,6 +943,20 @@ int Codec::finish_fetch(std::string *err) {
   return kOk;
 }
 
+// After the caller has waited for the queued batch: the decode checks, and while they report
+// the queued span passes unconverged (kResync), the remaining passes, every decode stage after
+// the sync again, then `tail` -- whatever the caller queues behind the decode, ending with its
+// wait -- and the checks again.
+template <class Tail>
+int Codec::settle_decode(int bgr, bool invert, Tail &&tail, std::string *err) {
+  int rc = check_decode(err);
+  while (rc == kResync) {
+    if ((rc = finish_sync(err)) || (rc = run_decode_post(bgr, invert, err)) || (rc = tail())) return rc;
+    rc = check_decode(err);
+  }
+  return rc;
+}
+
 // ---- public operations ---------------------------------------------------------------------------
 
 int Codec::encode(const uint8_t *const *imgs, const int *ws, const int *hs, int n, int pixel_format, int quality,
@@ -1050,6 +980,7 @@ int Codec::encode(const uint8_t *const *imgs, const int *ws, const int *hs, int 
   }
   const bool fast = (flags & kFlagFastDct) != 0;
   if ((rc = prepare_encode(ws, hs, offs.data(), n, quality, subsamp, fast, err))) return rc;
+  plan_ = DecodePlan();  // no decode, no switches: run_encode reads pixels (plan_.fuse off)
   CK(h_stage_.ensure(pix));
   CK(d_pix_.ensure(pix));
   pool_.run(n, [&](int f) {
@@ -1091,7 +1022,7 @@ int Codec::decode(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
     *err = "pixel_format must be TJPF_RGB (0) or TJPF_BGR (1)";
     return kInvalid;
   }
-  if ((rc = prepare_decode(jpegs, jsizes, n, flags, err))) return rc;
+  if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), false, err))) return rc;
   for (int f = 0; f < n; ++f) {
     const size_t need = (size_t)dfr_[(size_t)f].g.w * dfr_[(size_t)f].g.h * 3;
     if (!outs[f] || caps[f] < need) {
@@ -1100,15 +1031,13 @@ int Codec::decode(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
     }
   }
   if ((rc = run_decode(pixel_format, false, err))) return rc;
-  for (bool again = false;; again = true) {
-    if (again && ((rc = finish_sync(err)) || (rc = run_decode_post(pixel_format, false, err)))) return rc;
+  auto fetch_pixels = [&]() -> int {
     CK(h_out_.ensure(dpix_bytes_));
     CK(hipMemcpyAsync(h_out_.p, d_pix_.p, dpix_bytes_, hipMemcpyDeviceToHost, s_));
     CK(hipStreamSynchronize(s_));
-    rc = check_decode(err);
-    if (rc != kResync) break;
-  }
-  if (rc) return rc;
+    return kOk;
+  };
+  if ((rc = fetch_pixels()) || (rc = settle_decode(pixel_format, false, fetch_pixels, err))) return rc;
   pool_.run(n, [&](int f) {
     std::memcpy(outs[f], h_out_.as<uint8_t>() + dfr_[(size_t)f].out_off,
                 (size_t)dfr_[(size_t)f].g.w * dfr_[(size_t)f].g.h * 3);
@@ -1129,10 +1058,10 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
     *err = "empty batch";
     return kInvalid;
   }
-  static const bool trace = std::getenv("VF_JPEG_TRACE") != nullptr;
+  const JpegSwitches sw = JpegSwitches::read();
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
-  if ((rc = prepare_decode(jpegs, jsizes, n, flags, err))) return rc;
+  if ((rc = prepare_decode(jpegs, jsizes, n, flags, sw, true, err))) return rc;
   const auto t1 = clk::now();
   std::vector<int> ws((size_t)n), hs((size_t)n);
   std::vector<uint64_t> offs((size_t)n);
@@ -1140,12 +1069,8 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
   // the input's size (+25 % + 8 KB per frame, the rule before any batch); after the codec's first
   // batch, its measured output/input ratio + 6 % + 1 KB per frame (q95 input re-encoded at q85
   // halves: the fixed rule then copied 2.4x the output).  Short guesses take finish_fetch's
-  // second copy.
-  static const bool learn = [] {
-    const char *v = std::getenv("VF_JPEG_FETCH_LEARN");
-    return !(v && v[0] == '0');
-  }();
-  const double ratio = learn ? out_ratio_ : 0.0;
+  // second copy.  VF_JPEG_FETCH_LEARN=0: the fixed rule for this batch.
+  const double ratio = flag_on(sw.fetch_learn) ? out_ratio_ : 0.0;
   uint64_t guess = 0;
   in_bytes_ = 0;
   for (int f = 0; f < n; ++f) {
@@ -1156,9 +1081,7 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
     guess += ratio > 0 ? align_up((uint64_t)((double)jsizes[f] * ratio * 1.06) + 1024, 64)
                        : align_up(jsizes[f] + jsizes[f] / 4 + 8192, 64);
   }
-  const bool fast = (flags & kFlagFastDct) != 0;
-  if ((rc = prepare_encode(ws.data(), hs.data(), offs.data(), n, quality, subsamp, fast, err))) return rc;
-  fuse_ = fuse_enabled();
+  if ((rc = prepare_encode(ws.data(), hs.data(), offs.data(), n, quality, subsamp, plan_.enc_fast, err))) return rc;
   const auto t2 = clk::now();
   {
     std::unique_lock<std::mutex> gl;
@@ -1167,16 +1090,15 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
       if (gate_->last) CK(hipStreamWaitEvent(s_, gate_->last, 0));
     }
     // decode (BGR, inverted: cv2.bitwise_not, inverter.py:41) straight into the encoder's input
-    enc_fast_ = fast;
     if ((rc = run_decode(1, true, err))) return rc;
-    if ((rc = run_encode(1, fast, err))) return rc;
+    if ((rc = run_encode(1, plan_.enc_fast, err))) return rc;
     if (gate_) {
       CK(hipEventRecord(ev_[9], s_));
       gate_->last = ev_[9];
     }
   }
   if ((rc = queue_fetch(guess, err))) return rc;
-  if (trace) {
+  if (plan_.trace) {
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     static const clk::time_point origin = t0;
     std::fprintf(stderr, "[vf_jpeg] submit codec %p n=%d at %.3f: prep_dec %.3f (parse %.3f loop %.3f stage %.3f) "
@@ -1204,20 +1126,21 @@ int Codec::wait_invert(size_t *total, std::string *err) {
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
   CK(hipEventSynchronize(done_));
-  int rc = check_decode(err);
-  while (rc == kResync) {  // more sync passes, then every stage after the sync again
-    if ((rc = finish_sync(err)) || (rc = run_decode_post(1, true, err)) || (rc = run_encode(1, enc_fast_, err)) ||
-        (rc = queue_fetch(guess_, err)))
-      return rc;
+  // everything from here on follows the plan submit_invert left: this may run on another thread,
+  // under another environment
+  int rc = settle_decode(1, true, [&]() -> int {
+    int r = run_encode(1, plan_.enc_fast, err);
+    if (!r) r = queue_fetch(guess_, err);
+    if (r) return r;
     CK(hipEventSynchronize(done_));
-    rc = check_decode(err);
-  }
+    return kOk;
+  }, err);
   if (rc) return rc;
   if ((rc = finish_fetch(err))) return rc;
   if (in_bytes_) out_ratio_ = (double)out_total_ / (double)in_bytes_;
   waited_ = true;
   *total = (size_t)out_total_;
-  if (std::getenv("VF_JPEG_TRACE"))
+  if (plan_.trace)
     std::fprintf(stderr, "[vf_jpeg] wait codec %p: %.3f ms, %llu B fetched (%s)\n", (void *)this,
                  std::chrono::duration<double, std::milli>(clk::now() - t0).count(),
                  (unsigned long long)out_total_, out_total_ > guess_ ? "second copy" : "one copy");
@@ -1280,7 +1203,7 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
     *err = "bench_invert: empty batch or iters <= 0";
     return kInvalid;
   }
-  if ((rc = prepare_decode(jpegs, jsizes, n, flags, err))) return rc;
+  if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), true, err))) return rc;
   std::vector<int> ws((size_t)n), hs((size_t)n);
   std::vector<uint64_t> offs((size_t)n);
   for (int f = 0; f < n; ++f) {
@@ -1288,9 +1211,8 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
     hs[(size_t)f] = dfr_[(size_t)f].g.h;
     offs[(size_t)f] = dfr_[(size_t)f].out_off;
   }
-  const bool fast = (flags & kFlagFastDct) != 0;
+  const bool fast = plan_.enc_fast;
   if ((rc = prepare_encode(ws.data(), hs.data(), offs.data(), n, quality, subsamp, fast, err))) return rc;
-  fuse_ = fuse_enabled();
   float acc[8] = {0};
   double total_ms = 0;
   int passes = 0;
@@ -1322,13 +1244,12 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
   }
   stage_events_ = false;
   CK(hipStreamSynchronize(s_));
-  rc = check_decode(err);
-  while (rc == kResync) {
-    if ((rc = finish_sync(err)) || (rc = run_decode_post(1, true, err)) || (rc = run_encode(1, fast, err)))
-      return rc;
+  rc = settle_decode(1, true, [&]() -> int {
+    const int r = run_encode(1, fast, err);
+    if (r) return r;
     CK(hipStreamSynchronize(s_));
-    rc = check_decode(err);
-  }
+    return kOk;
+  }, err);
   if (rc) return rc;
   *ms = (float)(total_ms / iters);
   if (stage_ms) {

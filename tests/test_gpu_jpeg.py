@@ -386,6 +386,30 @@ def test_span_sync_unconverged_passes_resume(tj, monkeypatch, queued):
     assert [bytes(o) for o in tj.invert_batch_result(tj.invert_batch_submit(jpgs))] == want
 
 
+def test_submitted_batch_keeps_its_plan(tj, monkeypatch):
+    """A batch's decode plan is fixed when it is submitted: the switches change between submit and
+    result, on a batch whose queued span pass leaves the sync unconverged, so the result call runs
+    finish_sync and every stage after it (the write pass's form, the fused IDCT, the warm-up
+    among them).  Bit-exact with the oracle, and so is the next batch under the new settings.
+    (The same bytes come out of either plan: that nothing after the submit reads the environment
+    is what tests/test_jpeg_plan.py and the sources' single reader carry.)"""
+    monkeypatch.setenv("VF_JPEG_SYNC", "pass")
+    monkeypatch.setenv("VF_JPEG_SYNC_G", "4")
+    monkeypatch.setenv("VF_JPEG_SYNC_QUEUED", "1")
+    monkeypatch.setenv("VF_JPEG_CHUNKS", "1")
+    monkeypatch.setenv("VF_JPEG_SYNC_WARM", "2048")
+    jpgs = _span_sync_batch(90, J.TJSAMP_420)
+    want = [J.invert_jpeg(j) for j in jpgs]
+    ticket = tj.invert_batch_submit(jpgs)
+    monkeypatch.setenv("VF_JPEG_CHUNKS", "0")
+    monkeypatch.setenv("VF_JPEG_WRITE4", "0")
+    monkeypatch.setenv("VF_JPEG_FUSE_IDCT", "0")
+    monkeypatch.setenv("VF_JPEG_SYNC_WARM", "0")
+    monkeypatch.setenv("VF_JPEG_SYNC_G", "2")
+    assert [bytes(o) for o in tj.invert_batch_result(ticket)] == want
+    assert [bytes(o) for o in tj.invert_batch_result(tj.invert_batch_submit(jpgs))] == want
+
+
 @pytest.mark.parametrize("mode", ["spec", "pass"])
 def test_custom_tables_long_codes(tj, monkeypatch, mode):
     """Frames whose Huffman tables are not Annex K (tests/jpeg_recode.py): many codes longer
