@@ -32,6 +32,7 @@
 #include "vf_host_mem.h"
 #include "vf_internal.h"
 #include "vf_jpeg_codec.h"
+#include "vf_lut_split.h"
 
 #define VF_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -74,6 +75,12 @@ struct vf_ctx {
   std::atomic<uint64_t> jpeg_max_pixels{vf::jpeg::kDefaultMaxPixels};
   // vf_bench_device_ring's region events, created once (not inside a caller's timed region)
   hipEvent_t bench_ev[2] = {nullptr, nullptr};
+  // vf_lut_frames_host: a stream and one input and one output device buffer of lut_cap (+ slack)
+  // bytes, created by the first call; lut_cap is the engine's slot size
+  std::mutex lut_mu;
+  size_t lut_cap = 0;
+  hipStream_t lut_stream = nullptr;
+  uint8_t *lut_din = nullptr, *lut_dout = nullptr;
 };
 
 namespace {
@@ -241,12 +248,20 @@ VF_EXPORT int vf_create(int device, size_t max_frame_bytes, int max_batch, vf_ct
     delete ctx;
     return st;
   }
+  ctx->lut_cap = slot;
   *out = ctx;
   return VF_OK;
 }
 
 VF_EXPORT int vf_destroy(vf_ctx *ctx) {
   if (!ctx) return VF_OK;
+  if (ctx->lut_stream) {
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->lut_stream);
+    (void)hipFree(ctx->lut_din);
+    (void)hipFree(ctx->lut_dout);
+    (void)hipStreamDestroy(ctx->lut_stream);
+  }
   for (vf::jpeg::Codec *c : ctx->jpeg_all) delete c;  // each synchronises its stream first
   delete ctx->engine;  // finishes queued jobs first
   for (hipEvent_t e : ctx->bench_ev)
@@ -348,6 +363,101 @@ VF_EXPORT int vf_invert_device_frames(vf_ctx *ctx, const void *const *dsrcs, voi
   VF_HIP(ctx, hipSetDevice(ctx->device));
   VF_HIP(ctx, vf::launch_invert_frames(dsrcs, ddsts, nbytes, n, total_bytes, ctx->cfg,
                                        (hipStream_t)stream));
+  return VF_OK;
+}
+
+// ---- 256-entry table filter (cv2.LUT) on raw frames ------------------------------------------
+
+namespace {
+
+int check_table(vf_ctx *ctx, const char *fn, const uint8_t *table, int channels) {
+  if (!table) return set_err(ctx, VF_E_INVALID, 0, "%s: table is NULL", fn);
+  if (channels != 1 && channels != 3)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: channels=%d, a table has 1 or 3", fn, channels);
+  return VF_OK;
+}
+
+// vf_lut_frames_host's stream and device buffers (ctx->lut_mu held).
+int lut_staging(vf_ctx *ctx, size_t alloc) {
+  if (ctx->lut_stream) return VF_OK;
+  hipStream_t st = nullptr;
+  VF_HIP(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  void *din = nullptr, *dout = nullptr;
+  hipError_t e = hipMalloc(&din, alloc);
+  if (e == hipSuccess) e = hipMalloc(&dout, alloc);
+  if (e != hipSuccess) {
+    (void)hipFree(din);
+    (void)hipStreamDestroy(st);
+    return set_err(ctx, VF_E_NOMEM, (int)e, "vf_lut_frames_host: hipMalloc(%zu) failed: %s", alloc, hipGetErrorString(e));
+  }
+  ctx->lut_din = static_cast<uint8_t *>(din);
+  ctx->lut_dout = static_cast<uint8_t *>(dout);
+  ctx->lut_stream = st;
+  return VF_OK;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_lut_device(vf_ctx *ctx, const void *dsrc, void *ddst, size_t nbytes, const uint8_t *table,
+                            int channels, void *stream) {
+  VF_CHECK_CTX(ctx);
+  int rc = check_table(ctx, "vf_lut_device", table, channels);
+  if (rc != VF_OK) return rc;
+  if (channels == 3 && nbytes % 3 != 0)
+    return set_err(ctx, VF_E_INVALID, 0, "vf_lut_device: %zu bytes are not whole 3-channel pixels", nbytes);
+  if (nbytes == 0) return VF_OK;
+  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "vf_lut_device: NULL buffer");
+  if (overlaps_partially((const uint8_t *)dsrc, (const uint8_t *)ddst, nbytes))
+    return set_err(ctx, VF_E_INVALID, 0, "vf_lut_device: src and dst partially overlap");
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, vf::launch_lut(dsrc, ddst, nbytes, table, channels, 0, ctx->cfg, (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_lut_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const size_t *nbytes,
+                                 int n, const uint8_t *table, int channels) {
+  VF_CHECK_CTX(ctx);
+  int rc = check_table(ctx, "vf_lut_frames_host", table, channels);
+  if (rc != VF_OK) return rc;
+  std::vector<vf::Seg> segs;
+  if ((rc = frames_to_segs(ctx, "vf_lut_frames_host", srcs, dsts, nbytes, n, &segs)) != VF_OK) return rc;
+  std::vector<vf::lut::Frame> frames;
+  frames.reserve(segs.size());
+  for (const vf::Seg &sg : segs) {
+    if (channels == 3 && sg.len % 3 != 0)
+      return set_err(ctx, VF_E_INVALID, 0, "vf_lut_frames_host: a frame of %zu bytes is not whole 3-channel pixels",
+                     sg.len);
+    frames.push_back(vf::lut::Frame{sg.src, sg.dst, sg.len});
+  }
+  if (frames.empty()) return VF_OK;
+  std::lock_guard<std::mutex> lk(ctx->lut_mu);
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  // a piece sits in both device buffers at its caller pointers' offsets mod 16 past a 16-B
+  // boundary, so the copies and the kernel see the caller's alignment: up to 15 bytes of slack
+  const size_t cap = ctx->lut_cap, alloc = ((cap + 15 + 15) & ~(size_t)15);
+  if ((rc = lut_staging(ctx, alloc)) != VF_OK) return rc;
+  const std::vector<vf::lut::Launch> ls = vf::lut::split(frames, cap, channels);
+  hipStream_t st = ctx->lut_stream;
+  std::vector<size_t> at(ls.size());
+  for (size_t i = 0; i < ls.size();) {
+    // one fill of the buffers: upload and filter the pieces that fit, download them, wait
+    size_t cur = 0, j = i;
+    for (; j < ls.size(); ++j) {
+      const size_t room = (ls[j].len + 15 + 15) & ~(size_t)15;
+      if (cur + room > alloc) break;
+      const uint8_t *din = ctx->lut_din + cur + ((uintptr_t)ls[j].src & 15);
+      uint8_t *dout = ctx->lut_dout + cur + ((uintptr_t)ls[j].dst & 15);
+      at[j] = cur;
+      cur += room;
+      VF_HIP(ctx, hipMemcpyAsync(const_cast<uint8_t *>(din), ls[j].src, ls[j].len, hipMemcpyHostToDevice, st));
+      VF_HIP(ctx, vf::launch_lut(din, dout, ls[j].len, table, channels, ls[j].phase, ctx->cfg, st));
+    }
+    for (size_t k = i; k < j; ++k)
+      VF_HIP(ctx, hipMemcpyAsync(ls[k].dst, ctx->lut_dout + at[k] + ((uintptr_t)ls[k].dst & 15), ls[k].len,
+                                 hipMemcpyDeviceToHost, st));
+    VF_HIP(ctx, hipStreamSynchronize(st));
+    i = j;
+  }
   return VF_OK;
 }
 
@@ -678,42 +788,92 @@ VF_EXPORT int vf_jpeg_decode(vf_ctx *ctx, const uint8_t *const *jpegs, const siz
   return jpeg_status(ctx, rc, "vf_jpeg_decode: " + err);
 }
 
-VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
-                             int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes) {
-  VF_CHECK_CTX(ctx);
+namespace {
+
+// decode -> filter -> encode for vf_jpeg_invert (lut == nullptr: bitwise_not) and vf_jpeg_lut
+int jpeg_filter(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
+                int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes, const uint8_t *lut,
+                int channels) {
   if (n < 0 || (n > 0 && (!jpegs || !jpeg_sizes || !outs || !caps || !sizes)))
-    return set_err(ctx, VF_E_INVALID, 0, "vf_jpeg_invert: bad arguments");
-  if (n > 65535) return set_err(ctx, VF_E_INVALID, 0, "vf_jpeg_invert: at most 65535 frames per call");
+    return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
+  if (n > 65535) return set_err(ctx, VF_E_INVALID, 0, "%s: at most 65535 frames per call", fn);
   CodecLease lease(ctx);
   vf::jpeg::Codec *c = nullptr;
   int rc = jpeg_codec(ctx, lease, &c);
   if (rc) return rc;
   std::string err;
-  rc = c->invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, &err);
-  return jpeg_status(ctx, rc, "vf_jpeg_invert: " + err);
+  rc = c->invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, &err, lut, channels);
+  return jpeg_status(ctx, rc, std::string(fn) + ": " + err);
 }
 
-VF_EXPORT int vf_jpeg_invert_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
-                                    int quality, int subsamp, int flags, uint64_t *ticket) {
-  VF_CHECK_CTX(ctx);
+int jpeg_filter_submit(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                       int quality, int subsamp, int flags, uint64_t *ticket, const uint8_t *lut, int channels) {
   if (!ticket || n <= 0 || n > 65535 || !jpegs || !jpeg_sizes)
-    return set_err(ctx, VF_E_INVALID, 0, "vf_jpeg_invert_submit: bad arguments");
+    return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
   *ticket = 0;
   vf::jpeg::Codec *c = lease_nowait(ctx);
   if (!c)
-    return set_err(ctx, VF_E_INVALID, 0, "vf_jpeg_invert_submit: %zu batches already in flight; fetch one first",
-                   kMaxJpegJobs);
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %zu batches already in flight; fetch one first", fn, kMaxJpegJobs);
   std::string err;
-  const int rc = c->submit_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, &err);
+  const int rc = c->submit_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, &err, lut, channels);
   if (rc != VF_OK) {
     c->quiesce();  // a submit that failed after queueing work must not hand the codec on mid-flight
     give_back(ctx, c);
-    return jpeg_status(ctx, rc, "vf_jpeg_invert_submit: " + err);
+    return jpeg_status(ctx, rc, std::string(fn) + ": " + err);
   }
   std::lock_guard<std::mutex> lk(ctx->jpeg_mu);
   *ticket = ctx->jpeg_next_ticket++;
   ctx->jpeg_jobs[*ticket] = c;
   return VF_OK;
+}
+
+int jpeg_filter_bench(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                      int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms, const uint8_t *lut,
+                      int channels) {
+  if (n <= 0 || n > 65535 || !jpegs || !jpeg_sizes || !ms || iters <= 0)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
+  CodecLease lease(ctx);
+  vf::jpeg::Codec *c = nullptr;
+  int rc = jpeg_codec(ctx, lease, &c);
+  if (rc) return rc;
+  std::string err;
+  rc = c->bench_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms, &err, lut, channels);
+  return jpeg_status(ctx, rc, std::string(fn) + ": " + err);
+}
+
+}  // namespace
+
+VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
+                             int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  return jpeg_filter(ctx, "vf_jpeg_invert", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, nullptr, 0);
+}
+
+VF_EXPORT int vf_jpeg_invert_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                    int quality, int subsamp, int flags, uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  return jpeg_filter_submit(ctx, "vf_jpeg_invert_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket,
+                            nullptr, 0);
+}
+
+VF_EXPORT int vf_jpeg_lut(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                          const uint8_t *table, int channels, int quality, int subsamp, int flags,
+                          uint8_t *const *outs, const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  const int rc = check_table(ctx, "vf_jpeg_lut", table, channels);
+  if (rc != VF_OK) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_lut", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, table,
+                     channels);
+}
+
+VF_EXPORT int vf_jpeg_lut_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                 const uint8_t *table, int channels, int quality, int subsamp, int flags,
+                                 uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  const int rc = check_table(ctx, "vf_jpeg_lut_submit", table, channels);
+  if (rc != VF_OK) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_lut_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, table,
+                            channels);
 }
 
 VF_EXPORT int vf_jpeg_invert_query(vf_ctx *ctx, uint64_t ticket, int *done) {
@@ -767,13 +927,16 @@ VF_EXPORT int vf_jpeg_invert_scatter(vf_ctx *ctx, uint64_t ticket, uint8_t *cons
 VF_EXPORT int vf_jpeg_bench_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                                    int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms) {
   VF_CHECK_CTX(ctx);
-  if (n <= 0 || n > 65535 || !jpegs || !jpeg_sizes || !ms || iters <= 0)
-    return set_err(ctx, VF_E_INVALID, 0, "vf_jpeg_bench_invert: bad arguments");
-  CodecLease lease(ctx);
-  vf::jpeg::Codec *c = nullptr;
-  int rc = jpeg_codec(ctx, lease, &c);
-  if (rc) return rc;
-  std::string err;
-  rc = c->bench_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms, &err);
-  return jpeg_status(ctx, rc, "vf_jpeg_bench_invert: " + err);
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_invert", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
+                           stage_ms, nullptr, 0);
+}
+
+VF_EXPORT int vf_jpeg_bench_lut(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                const uint8_t *table, int channels, int quality, int subsamp, int flags, int iters,
+                                float *ms, float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  const int rc = check_table(ctx, "vf_jpeg_bench_lut", table, channels);
+  if (rc != VF_OK) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_lut", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
+                           table, channels);
 }

@@ -32,6 +32,11 @@ hipError_t launch_invert_frames(const void *const *dsrcs, void *const *ddsts,
                                 const size_t *nbytes, int n, size_t total_bytes,
                                 const LaunchCfg &cfg, hipStream_t stream);
 
+// ddst[i] = table[channel(i)][dsrc[i]] (vf_lut.hip): `table` is channels (1 or 3) planar 256-byte
+// tables in HOST memory, passed on by value; `phase` < channels is the channel of byte 0.
+hipError_t launch_lut(const void *dsrc, void *ddst, size_t nbytes, const uint8_t *table, int channels,
+                      uint32_t phase, const LaunchCfg &cfg, hipStream_t stream);
+
 // Up to kMappedMax page-locked host ranges, by their device addresses, inverted in place over
 // PCIe by one launch (vf_kernels.hip invert_mapped_kernel; passed by value as kernel arguments).
 constexpr int kMappedMax = 64;

@@ -73,14 +73,22 @@ hipError_t dec_write4(const DecSeg *sg, const DecFrame *fr, int nseg, uint32_t m
 // nmask: per-block stored-row masks from the write pass's chunked form (null: a cleared buffer)
 hipError_t dec_idct(const DecFrame *fr, int n, uint32_t max_blocks, const int16_t *coef, const int32_t *dcseq,
                     const uint8_t *nmask, uint8_t *planes, hipStream_t s);
+// A per-channel 256-entry filter table for the colour pass, passed to its kernels by value:
+// byte c * 256 + v is the output of value v in channel c of the BGR pixel (cv2.LUT's table,
+// planar; a one-channel table is stored three times).
+struct LutTable {
+  uint32_t w[192];
+};
+// lut: the table applied in place of the inversion (null: `invert` decides, as before)
 hipError_t dec_color(const DecFrame *fr, int n, int max_w, int max_h, const uint8_t *planes, uint8_t *pix,
-                     int bgr, int invert, const EncFrame *efr, int cm, hipStream_t s);
+                     int bgr, int invert, const EncFrame *efr, int cm, hipStream_t s, const LutTable *lut = nullptr);
 // the invert path's IDCT + colour in one pass for a batch of standard 4:2:2 frames (sampling 2x1,
 // 1x1, 1x1): the decoder planes stay in LDS, the encoder's sample planes come out
 hipError_t dec_idct_color422(const DecFrame *fr, int n, int max_w, int max_h, const int16_t *coef,
                              const int32_t *dcseq, const uint8_t *nmask, uint8_t *eplanes, const EncFrame *efr,
                              int invert, int one_row,
-                             hipStream_t s);  // one_row: the encoder's chroma is not vertically downsampled
+                             hipStream_t s,  // one_row: the encoder's chroma is not vertically downsampled
+                             const LutTable *lut = nullptr);
 
 hipError_t enc_fdct(const EncFrame *fr, int n, uint32_t max_blocks, const EncTables *tab, const uint8_t *pix,
                     int16_t *dcq, uint32_t *acbits, uint32_t *acscr, int bgr, int fastdct, int ch, int cv, int planes,

@@ -105,14 +105,17 @@ class Codec {
              int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes, std::string *err);
   int decode(const uint8_t *const *jpegs, const size_t *sizes, int n, int pixel_format, int flags,
              uint8_t *const *outs, const size_t *caps, std::string *err);
+  // lut (here and in submit_invert, bench_invert): `channels` (1 or 3) planar 256-byte tables
+  // applied to the decoded BGR pixels in place of the inversion (cv2.LUT); read during the call
   int invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
-             uint8_t *const *outs, const size_t *caps, size_t *out_sizes, std::string *err);
+             uint8_t *const *outs, const size_t *caps, size_t *out_sizes, std::string *err,
+             const uint8_t *lut = nullptr, int channels = 0);
   // invert() in three steps, so one host thread can keep batches of two codecs in flight:
   // submit_invert returns once everything is queued (inputs staged: the caller's buffers may go);
   // done_invert never blocks; wait_invert blocks and gives the packed output size; fetch_invert
   // copies the packed outputs (frame f at offs[f], sizes[f] bytes; out may be NULL).
   int submit_invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
-                    std::string *err);
+                    std::string *err, const uint8_t *lut = nullptr, int channels = 0);
   bool done_invert();
   int wait_invert(size_t *total, std::string *err);
   int fetch_invert(uint8_t *out, size_t cap, size_t *sizes, size_t *offs, std::string *err);
@@ -129,7 +132,8 @@ class Codec {
   // the device part of invert() `iters` times on resident inputs; mean wall ms per iteration,
   // stage_ms[0..6] = unstuff, sync, write, dc+idct, colour, fdct+huffman, stuffing; [7] = passes
   int bench_invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
-                   int iters, float *ms, float *stage_ms, std::string *err);
+                   int iters, float *ms, float *stage_ms, std::string *err, const uint8_t *lut = nullptr,
+                   int channels = 0);
 
  private:
   int init(std::string *err);
@@ -137,6 +141,7 @@ class Codec {
                      bool invert, std::string *err);  // parse, layout, uploads; resolves plan_
   int run_decode(int bgr, bool invert, std::string *err);
   int run_decode_post(int bgr, bool invert, std::string *err);  // write, DC, IDCT, colour
+  int set_filter(const uint8_t *lut, int channels, std::string *err);
   hipError_t span_pass(int p);
   int finish_sync(std::string *err);  // host-looped span passes after the queued ones
   int check_decode(std::string *err);
@@ -186,6 +191,8 @@ class Codec {
   uint32_t emax_blocks_ = 0, emax_tiles_ = 0;
   uint64_t eblocks_ = 0, ebits_bytes_ = 0;
   DevBuf d_eplanes_;  // the invert path's encoder sample planes (plan_.fuse)
+  bool has_lut_ = false;  // the invert path's filter is lut_ (else the inversion)
+  LutTable lut_ = {};
   int dcm_ = -1;  // k_color layout shared by the batch's frames (1..3, 0 general), -1 mixed
   DevBuf d_efr_, d_etab_, d_hdr_, d_esegs_, d_etsum_, d_etotals_, d_dcq_, d_acbits_, d_acscr_, d_bits_, d_pre_, d_bitoff_, d_stream_, d_ffcnt_,
       d_outsize_, d_pack_;

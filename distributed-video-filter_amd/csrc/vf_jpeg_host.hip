@@ -686,6 +686,7 @@ int Codec::run_decode_post(int bgr, bool invert, std::string *err) {
   const uint32_t *us_len = d_totals_.as<uint32_t>();
   const DecodePlan &pl = plan_;
   const int last = sync_slot_;
+  const LutTable *const lut = invert && has_lut_ ? &lut_ : nullptr;  // the batch's filter table (set_filter)
   // 3. block offsets of the subsequences, then the write pass
   // the segments' decoded block counts go straight to the page-locked h_dtot_ (check_decode)
   uint32_t *blocks_total = static_cast<uint32_t *>(dtot_dev_);
@@ -712,7 +713,7 @@ int Codec::run_decode_post(int bgr, bool invert, std::string *err) {
     CK(stage_event(4));  // the DC scan above is the dc_idct stage; the fused pass the colour stage
     CK(dec_idct_color422(fr, n, dmax_w_, dmax_h_, d_coef_.as<int16_t>(), d_dcpred_.as<int32_t>(), nmask,
                          d_eplanes_.as<uint8_t>(), d_efr_.as<EncFrame>(), invert ? 1 : 0, kSampV[esub_] == 1 ? 1 : 0,
-                         s_));
+                         s_, lut));
     CK(stage_event(5));
     return kOk;
   }
@@ -720,7 +721,7 @@ int Codec::run_decode_post(int bgr, bool invert, std::string *err) {
   CK(stage_event(4));
   // the invert path (pl.fuse): the encoder's sample planes instead of pixels (enc_sample_rows)
   CK(dec_color(fr, n, dmax_w_, dmax_h_, d_planes_.as<uint8_t>(), pl.fuse ? d_eplanes_.as<uint8_t>() : d_pix_.as<uint8_t>(),
-               bgr, invert ? 1 : 0, pl.fuse ? d_efr_.as<EncFrame>() : nullptr, dcm_, s_));
+               bgr, invert ? 1 : 0, pl.fuse ? d_efr_.as<EncFrame>() : nullptr, dcm_, s_, lut));
   CK(stage_event(5));
   return kOk;
 }
@@ -1049,11 +1050,28 @@ int Codec::decode(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
 // submit_invert (parse, stage, queue every upload, kernel and download; returns without
 // waiting for the GPU), wait_invert (the done event, the decode checks, the packed layout),
 // fetch_invert (copy-out).  invert() is the three in a row.
+// The filter of the invert path's next batch: cv2.LUT with `channels` (1 or 3) planar 256-byte
+// tables for the BGR pixel's channels, or, with no table, cv2.bitwise_not.  The codec keeps a
+// copy, so a batch resynchronised at wait_invert runs its colour pass with the same table.
+int Codec::set_filter(const uint8_t *lut, int channels, std::string *err) {
+  has_lut_ = lut != nullptr;
+  if (!lut) return kOk;
+  if (channels != 1 && channels != 3) {
+    has_lut_ = false;
+    *err = "table channels must be 1 or 3";
+    return kInvalid;
+  }
+  uint8_t *t = reinterpret_cast<uint8_t *>(lut_.w);
+  for (int c = 0; c < 3; ++c) std::memcpy(t + 256 * c, lut + (channels == 3 ? 256 * c : 0), 256);
+  return kOk;
+}
+
 int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp,
-                         int flags, std::string *err) {
+                         int flags, std::string *err, const uint8_t *lut, int channels) {
   int rc = init(err);
   if (rc) return rc;
   waited_ = false;
+  if ((rc = set_filter(lut, channels, err))) return rc;
   if (n <= 0) {
     *err = "empty batch";
     return kInvalid;
@@ -1186,9 +1204,10 @@ int Codec::fetch_invert(uint8_t *out, size_t cap, size_t *sizes, size_t *offs, s
 }
 
 int Codec::invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp, int flags,
-                  uint8_t *const *outs, const size_t *caps, size_t *sizes, std::string *err) {
+                  uint8_t *const *outs, const size_t *caps, size_t *sizes, std::string *err, const uint8_t *lut,
+                  int channels) {
   if (n <= 0) return init(err);
-  int rc = submit_invert(jpegs, jsizes, n, quality, subsamp, flags, err);
+  int rc = submit_invert(jpegs, jsizes, n, quality, subsamp, flags, err, lut, channels);
   size_t total = 0;
   if (!rc) rc = wait_invert(&total, err);
   if (!rc) rc = copy_out(outs, caps, sizes, err);
@@ -1196,13 +1215,15 @@ int Codec::invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
 }
 
 int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp,
-                        int flags, int iters, float *ms, float *stage_ms, std::string *err) {
+                        int flags, int iters, float *ms, float *stage_ms, std::string *err, const uint8_t *lut,
+                        int channels) {
   int rc = init(err);
   if (rc) return rc;
   if (n <= 0 || iters <= 0) {
     *err = "bench_invert: empty batch or iters <= 0";
     return kInvalid;
   }
+  if ((rc = set_filter(lut, channels, err))) return rc;
   if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), true, err))) return rc;
   std::vector<int> ws((size_t)n), hs((size_t)n);
   std::vector<uint64_t> offs((size_t)n);

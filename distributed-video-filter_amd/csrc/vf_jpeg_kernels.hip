@@ -2124,8 +2124,12 @@ __device__ __forceinline__ void up2(const int cs[6], int i0, int dw, bool fancy,
   }
 }
 
-// jdcolor.c ycc_rgb_convert (grayscale: replicated) of 8 pixels, inverted when asked
-__device__ __forceinline__ void ycc8(const int v[3][8], int ncomp, int bgr, int invert, uint8_t o[24]) {
+// jdcolor.c ycc_rgb_convert (grayscale: replicated) of 8 pixels, inverted when asked.
+// LUT: instead of the inversion, each channel through its 256-entry table (cv2.LUT on the BGR
+// frame: lut[0..255] is B's, [256..511] G's, [512..767] R's; the workgroup's copy in LDS).
+template <bool LUT = false>
+__device__ __forceinline__ void ycc8(const int v[3][8], int ncomp, int bgr, int invert, uint8_t o[24],
+                                     const uint8_t *lut = nullptr) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     uint32_t r, gg, b;
@@ -2137,7 +2141,11 @@ __device__ __forceinline__ void ycc8(const int v[3][8], int ncomp, int bgr, int 
       gg = clamp255(v[0][j] + ((__mul24(-22554, xcb) + 32768 - __mul24(46802, xcr)) >> 16));
       b = clamp255(v[0][j] + ((__mul24(116130, xcb) + 32768) >> 16));
     }
-    if (invert) {
+    if constexpr (LUT) {
+      r = lut[512 + r];
+      gg = lut[256 + gg];
+      b = lut[b];
+    } else if (invert) {
       r ^= 0xFF;
       gg ^= 0xFF;
       b ^= 0xFF;
@@ -2157,8 +2165,9 @@ __device__ __forceinline__ void unpack8(uint2 q, int v[8]) {
 // the chroma samples they need (+1 neighbour each side) for 2x horizontal subsampling, and
 // three 8-byte stores of interleaved output when the row is 8-byte aligned.
 // The 8 output pixels of row y from x0 (24 bytes of interleaved output in o).
+template <bool LUT = false>
 __device__ __forceinline__ void color8(const DecFrame &F, const Geom &g, const uint8_t *__restrict__ planes, int y,
-                                       int x0, int bgr, int invert, uint8_t o[24]) {
+                                       int x0, int bgr, int invert, uint8_t o[24], const uint8_t *lut = nullptr) {
   int v[3][8];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -2196,7 +2205,7 @@ __device__ __forceinline__ void color8(const DecFrame &F, const Geom &g, const u
         v[k][j] = up_sample(p, pw, dw, dh, he, ve, fancy && he <= 2 && ve <= 2, min(x0 + j, g.w - 1), y);
     }
   }
-  ycc8(v, g.ncomp, bgr, invert, o);
+  ycc8<LUT>(v, g.ncomp, bgr, invert, o, lut);
 }
 
 // jccolor.c rgb_ycc_convert for one component over a pixel's bytes in memory order:
@@ -2402,10 +2411,10 @@ struct GlobalPlanes {
   }
 };
 
-template <int MODE, bool ENC, typename PL, bool ONE = false>
+template <int MODE, bool ENC, typename PL, bool ONE = false, bool LUT = false>
 __device__ __forceinline__ void color_rows(const DecFrame &F, const Geom &g, const PL &pl,
                                            uint8_t *__restrict__ pix, const EncFrame *__restrict__ efr, int y0, int x0,
-                                           bool two, int bgr, int invert) {
+                                           bool two, int bgr, int invert, const uint8_t *lut = nullptr) {
   const int y1 = two ? y0 + 1 : y0;
   int v0[3][8], v1[3][8];
   if constexpr (MODE == 0) {
@@ -2492,15 +2501,17 @@ __device__ __forceinline__ void color_rows(const DecFrame &F, const Geom &g, con
         const uint32_t r = clamp255(yy + ((__mul24(91881, xcr) + 32768) >> 16));
         const uint32_t gg = clamp255(yy + ((__mul24(-22554, xcb) + 32768 - __mul24(46802, xcr)) >> 16));
         const uint32_t b = clamp255(yy + ((__mul24(116130, xcb) + 32768) >> 16));
-        const uint32_t px = (r | gg << 8 | b << 16) ^ (invert ? 0xFFFFFFu : 0u);
+        uint32_t px;
+        if constexpr (LUT) px = lut[512 + r] | (uint32_t)lut[256 + gg] << 8 | (uint32_t)lut[b] << 16;
+        else px = (r | gg << 8 | b << 16) ^ (invert ? 0xFFFFFFu : 0u);
         if (rw) p1[j] = two ? px : p0[j];
         else p0[j] = px;
       }
     return enc_store_rows<ONE>(efr[blockIdx.z], pix, p0, p1, y0, x0, g.w);
   }
   uint8_t o0[24], o1[24];
-  ycc8(v0, 3, bgr, invert, o0);
-  ycc8(v1, 3, bgr, invert, o1);
+  ycc8<LUT>(v0, 3, bgr, invert, o0, lut);
+  ycc8<LUT>(v1, 3, bgr, invert, o1, lut);
   // both destinations before the first store (after it, F's fields were re-loaded with a wait)
   const int w = g.w;
   uint8_t *const d0 = pix + F.out_off + ((size_t)y0 * w + x0) * 3, *const d1 = d0 + (size_t)w * 3;
@@ -2516,10 +2527,38 @@ __device__ __forceinline__ void color_rows(const DecFrame &F, const Geom &g, con
 // set its occupancy (with all paths in one kernel, the fused form needed 127 VGPRs).
 // (The fused 2x1 form: 96 VGPRs, 5 waves per SIMD; held to 80 for 6 waves it spilled two
 // registers and ran no faster, 102.5 vs 103 us at 1080p x 32.)
-template <bool ENC, int CM>
+// LUT: a 256-entry table per channel in place of the inversion (cv2.LUT between the decode and
+// the encode); the last argument is then the table, by value, staged in LDS before the early
+// return of threads outside the frame: they still take part in the barrier.
+template <bool LUT>
+struct ColorFilter {  // the colour kernels' last argument: the `invert` flag
+  typedef int Arg;
+  static __device__ __forceinline__ int invert(int f) { return f; }
+};
+template <>
+struct ColorFilter<true> {  // ... or the table
+  typedef LutTable Arg;
+  static __device__ __forceinline__ int invert(const LutTable &) { return 0; }
+};
+
+// The workgroup's copy of a by-value table (192 dwords of kernel arguments) in LDS.  Every
+// thread of the workgroup calls it; the caller's next barrier publishes it.
+__device__ __forceinline__ void stage_lut(uint32_t *s_lut, const LutTable &tab) {
+  if (threadIdx.x < 192) s_lut[threadIdx.x] = tab.w[threadIdx.x];
+}
+
+template <bool ENC, int CM, bool LUT = false>
 __global__ __launch_bounds__(256) void k_color(const DecFrame *__restrict__ fr, const uint8_t *__restrict__ planes,
                                                uint8_t *__restrict__ pix, const EncFrame *__restrict__ efr, int bgr,
-                                               int invert) {
+                                               const typename ColorFilter<LUT>::Arg filt) {
+  const uint8_t *lut = nullptr;
+  if constexpr (LUT) {
+    __shared__ uint32_t s_lut[192];
+    stage_lut(s_lut, filt);
+    __syncthreads();
+    lut = reinterpret_cast<const uint8_t *>(s_lut);
+  }
+  const int invert = ColorFilter<LUT>::invert(filt);
   const DecFrame &F = fr[blockIdx.z];
   const Geom &g = F.g;
   const int y0 = blockIdx.y * 2, x0 = (blockIdx.x * 256 + threadIdx.x) * 8;
@@ -2530,12 +2569,12 @@ __global__ __launch_bounds__(256) void k_color(const DecFrame *__restrict__ fr, 
   // issued up front
   const uint32_t cm = CM >= 0 ? (uint32_t)CM : (F.flags >> 1) & 3u;
   const GlobalPlanes gp{planes, F};
-  if (cm == 1) return color_rows<0, ENC>(F, g, gp, pix, efr, y0, x0, two, bgr, invert);
-  if (cm == 2) return color_rows<1, ENC>(F, g, gp, pix, efr, y0, x0, two, bgr, invert);
-  if (cm == 3) return color_rows<2, ENC>(F, g, gp, pix, efr, y0, x0, two, bgr, invert);
+  if (cm == 1) return color_rows<0, ENC, GlobalPlanes, false, LUT>(F, g, gp, pix, efr, y0, x0, two, bgr, invert, lut);
+  if (cm == 2) return color_rows<1, ENC, GlobalPlanes, false, LUT>(F, g, gp, pix, efr, y0, x0, two, bgr, invert, lut);
+  if (cm == 3) return color_rows<2, ENC, GlobalPlanes, false, LUT>(F, g, gp, pix, efr, y0, x0, two, bgr, invert, lut);
   uint8_t o0[24], o1[24];
-  color8(F, g, planes, y0, x0, bgr, invert, o0);
-  color8(F, g, planes, two ? y0 + 1 : y0, x0, bgr, invert, o1);
+  color8<LUT>(F, g, planes, y0, x0, bgr, invert, o0, lut);
+  color8<LUT>(F, g, planes, two ? y0 + 1 : y0, x0, bgr, invert, o1, lut);
   if constexpr (ENC) return enc_sample_rows(efr[blockIdx.z], pix, o0, o1, y0, x0, g.w, bgr);
   const int w = g.w;
   uint8_t *const d0 = pix + F.out_off + ((size_t)y0 * w + x0) * 3;
@@ -2568,11 +2607,13 @@ struct StripPlanes {
 
 // ONE: the encoder's chroma is not vertically downsampled (its rows are independent), so every
 // thread converts one 8-pixel row (240 threads busy); else 8 pixels x 2 rows (120 threads).
-template <bool ONE>
+// LUT: the last argument is the table, by value, in place of the `invert` flag; it is staged in
+// LDS before the first barrier, which every thread of a workgroup that has a strip reaches.
+template <bool ONE, bool LUT = false>
 __global__ __launch_bounds__(256) void k_idct_color422(const DecFrame *__restrict__ fr, const int16_t *coef,
                                                        const int32_t *dcseq, const uint8_t *nmask,
                                                        uint8_t *__restrict__ eplanes, const EncFrame *__restrict__ efr,
-                                                       int invert) {
+                                                       const typename ColorFilter<LUT>::Arg filt) {
   const DecFrame &F = fr[blockIdx.z];
   const Geom &g = F.g;
   const int mcux = g.mcux, my = blockIdx.y, m0 = blockIdx.x * kStripMcus;
@@ -2616,6 +2657,12 @@ __global__ __launch_bounds__(256) void k_idct_color422(const DecFrame *__restric
   if (t < 192) s_qz[t >> 6][kZigOf[t & 63]] = F.q[t >> 6][t & 63];
   if (t < 64) s_pos[t] = kIdctPos[t];
   if (t < 8) s_col[t] = kIdctCol[t];
+  const uint8_t *lut = nullptr;
+  if constexpr (LUT) {
+    __shared__ uint32_t s_lut[192];
+    stage_lut(s_lut, filt);
+    lut = reinterpret_cast<const uint8_t *>(s_lut);
+  }
   __syncthreads();
   const uint2 pos8 = *reinterpret_cast<const uint2 *>(&s_pos[r * 8]);
   const uint32_t colg = s_col[r];
@@ -2686,7 +2733,8 @@ __global__ __launch_bounds__(256) void k_idct_color422(const DecFrame *__restric
   const int y0 = my * 8 + kRows * rp, x0 = m0 * 16 + px * 8;
   if (y0 >= g.h || x0 >= g.w) return;
   const StripPlanes sp{s_y, s_cb, s_cr, my * 8, m0 * 16, (m0 - 1) * 8};
-  color_rows<1, true, StripPlanes, ONE>(F, g, sp, eplanes, efr, y0, x0, !ONE && y0 + 1 < g.h, 0, invert);
+  color_rows<1, true, StripPlanes, ONE, LUT>(F, g, sp, eplanes, efr, y0, x0, !ONE && y0 + 1 < g.h, 0,
+                                             ColorFilter<LUT>::invert(filt), lut);
 }
 
 // ---- encoder: colour + downsampling + FDCT + quantisation -----------------------------------
@@ -3601,10 +3649,14 @@ hipError_t dec_idct(const DecFrame *__restrict__ fr, int n, uint32_t max_blocks,
 }
 
 hipError_t dec_color(const DecFrame *__restrict__ fr, int n, int max_w, int max_h, const uint8_t *planes, uint8_t *pix, int bgr,
-                     int invert, const EncFrame *efr, int cm, hipStream_t s) {
+                     int invert, const EncFrame *efr, int cm, hipStream_t s, const LutTable *lut) {
   if (n <= 0 || max_w <= 0 || max_h <= 0) return hipSuccess;
   const dim3 grid((unsigned)((max_w + 2047) / 2048), (unsigned)((max_h + 1) / 2), (unsigned)n);
-#define VF_COLOR(E, C) hipLaunchKernelGGL((k_color<E, C>), grid, dim3(256), 0, s, fr, planes, pix, efr, bgr, invert)
+#define VF_COLOR(E, C)                                                                                    \
+  do {                                                                                                    \
+    if (lut) hipLaunchKernelGGL((k_color<E, C, true>), grid, dim3(256), 0, s, fr, planes, pix, efr, bgr, *lut); \
+    else hipLaunchKernelGGL((k_color<E, C>), grid, dim3(256), 0, s, fr, planes, pix, efr, bgr, invert);  \
+  } while (0)
   if (efr) {
     if (cm == 0) VF_COLOR(true, 0);
     else if (cm == 1) VF_COLOR(true, 1);
@@ -3624,11 +3676,15 @@ hipError_t dec_color(const DecFrame *__restrict__ fr, int n, int max_w, int max_
 
 hipError_t dec_idct_color422(const DecFrame *__restrict__ fr, int n, int max_w, int max_h, const int16_t *coef,
                              const int32_t *dcseq, const uint8_t *nmask, uint8_t *eplanes, const EncFrame *efr,
-                             int invert, int one_row, hipStream_t s) {
+                             int invert, int one_row, hipStream_t s, const LutTable *lut) {
   if (n <= 0 || max_w <= 0 || max_h <= 0) return hipSuccess;
   const unsigned mcux = (unsigned)((max_w + 15) / 16), mcuy = (unsigned)((max_h + 7) / 8);
   const dim3 grid((mcux + kStripMcus - 1) / kStripMcus, mcuy, (unsigned)n);
-  if (one_row)
+  if (lut && one_row)
+    hipLaunchKernelGGL((k_idct_color422<true, true>), grid, dim3(256), 0, s, fr, coef, dcseq, nmask, eplanes, efr, *lut);
+  else if (lut)
+    hipLaunchKernelGGL((k_idct_color422<false, true>), grid, dim3(256), 0, s, fr, coef, dcseq, nmask, eplanes, efr, *lut);
+  else if (one_row)
     hipLaunchKernelGGL(k_idct_color422<true>, grid, dim3(256), 0, s, fr, coef, dcseq, nmask, eplanes, efr, invert);
   else
     hipLaunchKernelGGL(k_idct_color422<false>, grid, dim3(256), 0, s, fr, coef, dcseq, nmask, eplanes, efr, invert);

@@ -1,0 +1,235 @@
+// vf_lut.hip — the 256-entry table filter on raw frames: dst[i] = table[channel(i)][src[i]],
+// cv2.LUT(frame, table) for uint8 frames of 1 or 3 interleaved channels.  Every per-pixel
+// filter of the reference's plugin slot (inverter.py:41) that is not bitwise_not -- gamma,
+// levels, threshold, posterize, per-channel curves -- is one of these tables.
+//
+// The memory side is invert_stream_kernel's (vf_stream.h): 16 B per lane per access, U = 4
+// independent loads in flight, nontemporal loads and stores, grid-stride over whole tiles, the
+// head and tail bytes of an unaligned range done bytewise by block 0.  The filter itself is
+// one LDS byte read per input byte:
+//   * the table arrives BY VALUE as a kernel argument (768 B: three planar 256-byte tables, a
+//     one-channel table stored three times), so a launch needs no device allocation, nothing
+//     has a lifetime and the launch stays asynchronous on the caller's stream; each workgroup
+//     copies it into LDS once, then runs its tiles;
+//   * 16 = 1 (mod 3), so byte k of body vector i has channel (c0 + i + k) % 3 with c0 the
+//     channel of the body's first byte; 256 = 1 (mod 3) too, so the U vectors of a lane's tile
+//     are one rotation apart and a lane keeps three table offsets, rotated per vector at
+//     compile time and advanced by (grid stride % 3) per tile;
+//   * the LDS address of a lookup is (channel << 8 | byte), built by one v_perm_b32.
+// LAYOUT (VF_LUT_LAYOUT in the environment, read once; for measurements): 0 = the table as it
+// is, 768 B, four entries per LDS dword (the default: the faster of the two, at 99 % of the
+// invert kernel's rate); 1 = one entry per dword, 3 KiB.  DESIGN.md 15 records what each
+// measured, and what else was tried and dropped.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include <cstring>
+
+#include "vf_env.h"
+#include "vf_internal.h"
+#include "vf_stream.h"
+
+namespace vf {
+
+namespace {
+
+struct LutArg {
+  uint32_t w[192];  // byte c * 256 + v: the output of value v in channel c
+};
+
+template <int LAYOUT>
+struct LutLds;
+
+template <>
+struct LutLds<0> {
+  static constexpr int kWords = 192;
+  static __device__ __forceinline__ void stage(uint32_t *s, const LutArg &tab) {
+    if (threadIdx.x < 192) s[threadIdx.x] = tab.w[threadIdx.x];
+  }
+  static __device__ __forceinline__ uint32_t at(const uint32_t *s, uint32_t idx) {
+    return reinterpret_cast<const uint8_t *>(s)[idx];
+  }
+};
+
+template <>
+struct LutLds<1> {
+  static constexpr int kWords = 768;
+  static __device__ __forceinline__ void stage(uint32_t *s, const LutArg &tab) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const uint32_t i = (uint32_t)k * kBlock + threadIdx.x;
+      s[i] = (tab.w[i >> 2] >> (8 * (i & 3))) & 0xFF;
+    }
+  }
+  static __device__ __forceinline__ uint32_t at(const uint32_t *s, uint32_t idx) { return s[idx]; }
+};
+
+__device__ __forceinline__ uint32_t mod3_inc(uint32_t c, uint32_t by) {  // (c + by) % 3 for c, by < 3
+  c += by;
+  return c >= 3 ? c - 3 : c;
+}
+
+// One 16-B vector through the table.  h[m] = the channel of its byte m (m = 0..2; byte p has
+// channel h[p % 3]); ROT rotates that by a compile-time count.
+template <bool C3, int LAYOUT, int ROT>
+__device__ __forceinline__ u32x4 lut16(const uint32_t *s, u32x4 v, const uint32_t h[3]) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  uint32_t o[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      // byte 0 = byte k of w[j], byte 1 = the channel, bytes 2 and 3 zero
+      const uint32_t idx = __builtin_amdgcn_perm(C3 ? h[(4 * j + k + ROT) % 3] : 0u, w[j], 0x0C0C0400u | (uint32_t)k);
+      r |= LutLds<LAYOUT>::at(s, idx) << (8 * k);
+    }
+    o[j] = r;
+  }
+  u32x4 out;
+  out.x = o[0];
+  out.y = o[1];
+  out.z = o[2];
+  out.w = o[3];
+  return out;
+}
+
+template <bool C3, int LAYOUT, int U, int J = 0>
+__device__ __forceinline__ void lut_tile(const uint32_t *s, const u32x4 (&v)[U], u32x4 *d, const uint32_t h[3]) {
+  if constexpr (J < U) {
+    st16<true>(d + J * kBlock, lut16<C3, LAYOUT, J % 3>(s, v[J], h));
+    lut_tile<C3, LAYOUT, U, J + 1>(s, v, d, h);
+  }
+}
+
+template <bool C3, int LAYOUT, int U, int J = 0>
+__device__ __forceinline__ void lut_partial(const uint32_t *s, const u32x4 *src, u32x4 *dst, uint64_t i0, uint64_t n16,
+                                            const uint32_t h[3]) {
+  if constexpr (J < U) {
+    const uint64_t i = i0 + (uint64_t)J * kBlock;
+    if (i < n16) st16<true>(dst + i, lut16<C3, LAYOUT, J % 3>(s, ld16<true>(src + i), h));
+    lut_partial<C3, LAYOUT, U, J + 1>(s, src, dst, i0, n16, h);
+  }
+}
+
+// Body: n16 aligned 16-B vectors at src/dst.  Head/tail: up to 15 bytes each, bytewise by block 0.
+// phases: bits 0-1 the channel of the body's first byte, 2-3 of the head's, 4-5 of the tail's.
+template <int U, bool C3, int LAYOUT>
+__global__ __launch_bounds__(kBlock) void lut_stream_kernel(
+    const u32x4 *__restrict__ src, u32x4 *__restrict__ dst, uint64_t n16,
+    const uint8_t *__restrict__ hsrc, uint8_t *__restrict__ hdst, uint32_t head,
+    const uint8_t *__restrict__ tsrc, uint8_t *__restrict__ tdst, uint32_t tail, uint32_t phases,
+    const LutArg tab) {
+  __shared__ uint32_t s[LutLds<LAYOUT>::kWords];
+  LutLds<LAYOUT>::stage(s, tab);
+  __syncthreads();
+  constexpr uint64_t TILE = (uint64_t)kBlock * U;
+  const uint64_t stride = (uint64_t)gridDim.x * TILE;
+  const uint32_t t = threadIdx.x;
+  uint64_t t0 = (uint64_t)blockIdx.x * TILE;  // wave-uniform tile start
+  // the channel of byte 0 of this lane's first vector, and how far a grid stride moves it
+  uint32_t c = C3 ? (uint32_t)(((phases & 3) + t0 + t) % 3) : 0;
+  const uint32_t step = C3 ? (uint32_t)(stride % 3) : 0;
+  for (; t0 + TILE <= n16; t0 += stride) {
+    const u32x4 *sp = src + t0 + t;
+    u32x4 v[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) v[j] = ld16<true>(sp + j * kBlock);
+    const uint32_t h[3] = {c, mod3_inc(c, 1), mod3_inc(c, 2)};
+    lut_tile<C3, LAYOUT, U>(s, v, dst + t0 + t, h);
+    c = mod3_inc(c, step);
+  }
+  if (t0 < n16) {  // the single partial tile, owned by whichever block reaches it
+    const uint32_t h[3] = {c, mod3_inc(c, 1), mod3_inc(c, 2)};
+    lut_partial<C3, LAYOUT, U>(s, src, dst, t0 + t, n16, h);
+  }
+  if (blockIdx.x == 0) {
+    const uint32_t hc = C3 ? ((phases >> 2) & 3) + t : 0, tc = C3 ? ((phases >> 4) & 3) + t : 0;
+    if (t < head) hdst[t] = (uint8_t)LutLds<LAYOUT>::at(s, (hc % 3) << 8 | hsrc[t]);
+    if (t < tail) tdst[t] = (uint8_t)LutLds<LAYOUT>::at(s, (tc % 3) << 8 | tsrc[t]);
+  }
+}
+
+// src and dst at different offsets mod 16: no common 16-B grid.  Bytewise, grid-stride; correct
+// at any alignment and an order of magnitude slower than the stream kernel (callers that care
+// keep the two congruent mod 16, as vf_lut_frames_host's staging does).
+template <bool C3>
+__global__ __launch_bounds__(kBlock) void lut_bytes_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+                                                           uint64_t n, uint32_t phase, const LutArg tab) {
+  __shared__ uint32_t s[LutLds<0>::kWords];
+  LutLds<0>::stage(s, tab);
+  __syncthreads();
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const uint32_t c = C3 ? (uint32_t)((phase + i) % 3) : 0;
+    dst[i] = (uint8_t)LutLds<0>::at(s, c << 8 | src[i]);
+  }
+}
+
+template <bool C3, int LAYOUT>
+hipError_t launch_lut_stream(const uint8_t *src, uint8_t *dst, size_t nbytes, uint32_t phase, const LutArg &tab,
+                             int max_blocks, hipStream_t stream) {
+  constexpr int U = 4;
+  // head (bytes until 16-B alignment), body (whole vectors), tail: launch_stream's split, with
+  // the channel of each part's first byte beside it
+  const uint32_t head = (uint32_t)((16 - ((uintptr_t)src & 15)) & 15);
+  const uint32_t h = head < nbytes ? head : (uint32_t)nbytes;
+  const uint64_t rest = nbytes - h;
+  const uint64_t n16 = rest >> 4;
+  const uint32_t tail = (uint32_t)(rest & 15);
+  constexpr uint64_t TILE = (uint64_t)kBlock * U;
+  const uint64_t nchunks = (n16 << 4) > kSplitBytes ? ((n16 << 4) + kChunkBytes - 1) / kChunkBytes : 1;
+  const uint64_t per = nchunks > 1 ? ((n16 + nchunks - 1) / nchunks + TILE - 1) / TILE * TILE : n16;
+  const uint8_t *bs = src + h;
+  uint8_t *bd = dst + h;
+  const uint32_t tail_ph = (uint32_t)((phase + h + n16) % 3);  // 16 = 1 (mod 3)
+  for (uint64_t c0 = 0, k = 0; k == 0 || c0 < n16; c0 += per, ++k) {
+    const uint64_t m = (n16 - c0) < per ? (n16 - c0) : per;
+    const bool first = k == 0, last = c0 + m >= n16;
+    const uint64_t tiles = (m + TILE - 1) / TILE;
+    uint64_t blocks = tiles ? tiles : 1;
+    if (blocks > (uint64_t)max_blocks) blocks = (uint64_t)max_blocks;
+    const uint32_t body_ph = (uint32_t)((phase + h + c0) % 3);
+    const uint32_t phases = body_ph | phase << 2 | tail_ph << 4;
+    hipLaunchKernelGGL((lut_stream_kernel<U, C3, LAYOUT>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+                       reinterpret_cast<const u32x4 *>(bs) + c0, reinterpret_cast<u32x4 *>(bd) + c0, m, src, dst,
+                       first ? h : 0u, bs + (n16 << 4), bd + (n16 << 4), last ? tail : 0u, phases, tab);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (last) break;
+  }
+  return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t launch_lut(const void *dsrc, void *ddst, size_t nbytes, const uint8_t *table, int channels, uint32_t phase,
+                      const LaunchCfg &cfg, hipStream_t stream) {
+  if (nbytes == 0) return hipSuccess;
+  if (!table || (channels != 1 && channels != 3) || phase >= (uint32_t)channels) return hipErrorInvalidValue;
+  LutArg tab;
+  uint8_t *tb = reinterpret_cast<uint8_t *>(tab.w);
+  for (int c = 0; c < 3; ++c) std::memcpy(tb + 256 * c, table + (channels == 3 ? 256 * c : 0), 256);
+  const uint8_t *src = static_cast<const uint8_t *>(dsrc);
+  uint8_t *dst = static_cast<uint8_t *>(ddst);
+  const bool c3 = channels == 3;
+  if (((uintptr_t)src ^ (uintptr_t)dst) & 15) {
+    // 16 bytes per thread and grid stride at the least, so short ranges take few workgroups
+    uint64_t blocks = (nbytes + (uint64_t)kBlock * 16 - 1) / ((uint64_t)kBlock * 16);
+    if (blocks > (uint64_t)cfg.max_blocks) blocks = (uint64_t)cfg.max_blocks;
+    if (c3) hipLaunchKernelGGL(lut_bytes_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, src, dst,
+                               (uint64_t)nbytes, phase, tab);
+    else hipLaunchKernelGGL(lut_bytes_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, src, dst,
+                            (uint64_t)nbytes, 0u, tab);
+    return hipGetLastError();
+  }
+  static const int layout = env_size("VF_LUT_LAYOUT", 0) == 1 ? 1 : 0;
+  if (layout == 1)
+    return c3 ? launch_lut_stream<true, 1>(src, dst, nbytes, phase, tab, cfg.max_blocks, stream)
+              : launch_lut_stream<false, 1>(src, dst, nbytes, 0, tab, cfg.max_blocks, stream);
+  return c3 ? launch_lut_stream<true, 0>(src, dst, nbytes, phase, tab, cfg.max_blocks, stream)
+            : launch_lut_stream<false, 0>(src, dst, nbytes, 0, tab, cfg.max_blocks, stream);
+}
+
+}  // namespace vf

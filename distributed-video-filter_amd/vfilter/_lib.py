@@ -83,6 +83,14 @@ SIGNATURES = {
     "vf_jpeg_invert_scatter": (ctypes.c_int, [_vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int)]),
     "vf_jpeg_bench_invert": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, _c_float_p, _c_float_p]),
+    "vf_lut_device": (ctypes.c_int, [_vp, _vp, _vp, _sz, _u8p, ctypes.c_int, _vp]),
+    "vf_lut_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _u8p, ctypes.c_int]),
+    "vf_jpeg_lut": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_lut_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_lut": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
 }
 
 
@@ -362,6 +370,29 @@ class Context:
         da = (ctypes.c_void_p * n)(*[_addr(d) for d in dsts])
         na = (ctypes.c_size_t * n)(*[int(b) for b in nbytes])
         self._check(self._lib.vf_invert_frames_host(self._ctx, sa, da, na, n))
+
+    # -- 256-entry table filter (cv2.LUT): vf_lut_* ---------------------------------------------
+    @staticmethod
+    def _table(table, channels: int) -> np.ndarray:
+        """``table`` (planar bytes, ``filters.as_table``'s first result) as an array to point at."""
+        t = np.frombuffer(table, dtype=np.uint8) if not isinstance(table, np.ndarray) else table
+        if t.dtype != np.uint8 or t.size != 256 * channels or not t.flags.c_contiguous:
+            raise ValueError("table must be channels x 256 contiguous uint8 (see vfilter.as_table)")
+        return t
+
+    def lut_frames_host(self, srcs: Sequence, dsts: Sequence, nbytes: Sequence[int], table, channels: int) -> None:
+        n = len(srcs)
+        if not (len(dsts) == n == len(nbytes)):
+            raise ValueError("srcs, dsts and nbytes must have the same length")
+        t = self._table(table, channels)
+        sa = (ctypes.c_void_p * n)(*[_addr(s) for s in srcs])
+        da = (ctypes.c_void_p * n)(*[_addr(d) for d in dsts])
+        na = (ctypes.c_size_t * n)(*[int(b) for b in nbytes])
+        self._check(self._lib.vf_lut_frames_host(self._ctx, sa, da, na, n, t.ctypes.data, channels))
+
+    def lut_device(self, dsrc: int, ddst: int, nbytes: int, table, channels: int, stream: int = 0) -> None:
+        t = self._table(table, channels)
+        self._check(self._lib.vf_lut_device(self._ctx, dsrc, ddst, nbytes, t.ctypes.data, channels, stream or None))
 
     # -- host -> host, asynchronous (page-locked buffers) -----------------------------------
     def invert_frames_async(self, srcs: Sequence, dsts: Sequence, nbytes: Sequence[int]) -> int:
@@ -678,6 +709,59 @@ class Context:
         self._check(self._lib.vf_jpeg_bench_invert(self._ctx, ja, js, n, quality, subsamp, flags, iters,
                                                    ctypes.byref(ms), st))
         names = ("unstuff", "huffman_sync", "huffman_write", "dc_idct", "color_invert", "fdct_huffman",
+                 "stuffing", "sync_passes")
+        return ms.value, dict(zip(names, [float(x) for x in st]))
+
+    # -- JPEG with a table in place of the inversion (vf_jpeg_lut*); tickets are invert tickets ----
+    def jpeg_lut(self, jpegs: Sequence, table, channels: int, quality: int, subsamp: int, flags: int = 0) -> list:
+        """decode -> cv2.LUT -> encode for every JPEG, fused on the GPU; returns bytes."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_lut_submit(jpegs, table, channels, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_lut_submit(self, jpegs: Sequence, table, channels: int, quality: int, subsamp: int,
+                        flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the table; collect with the ``jpeg_invert_result*`` methods."""
+        n = len(jpegs)
+        if n == 0:
+            raise ValueError("jpeg_lut_submit: empty batch")
+        t = self._table(table, channels)
+        srcs, ja = self._ptrs(jpegs)
+        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
+        tk = ctypes.c_uint64(0)
+        self._check(self._lib.vf_jpeg_lut_submit(self._ctx, ja, js, n, t.ctypes.data, channels, quality, subsamp,
+                                                 flags, ctypes.byref(tk)))
+        self.__dict__.setdefault("_jpeg_n", {})[tk.value] = n
+        return tk.value
+
+    def jpeg_lut_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, table, channels: int, quality: int,
+                              subsamp: int, flags: int = 0) -> int:
+        """``jpeg_lut_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        a = np.ascontiguousarray(addrs, np.uint64)
+        z = np.ascontiguousarray(sizes, np.uint64)
+        n = len(a)
+        if n == 0 or len(z) != n:
+            raise ValueError("jpeg_lut_submit_addrs: empty batch or sizes of another length")
+        t = self._table(table, channels)
+        tk = ctypes.c_uint64(0)
+        self._check(self._lib.vf_jpeg_lut_submit(self._ctx, a.ctypes.data, z.ctypes.data, n, t.ctypes.data, channels,
+                                                 quality, subsamp, flags, ctypes.byref(tk)))
+        self.__dict__.setdefault("_jpeg_n", {})[tk.value] = n
+        return tk.value
+
+    def jpeg_bench_lut(self, jpegs: Sequence, table, channels: int, quality: int, subsamp: int, flags: int = 0,
+                       iters: int = 10):
+        """``jpeg_bench_invert`` with the table in the colour stage."""
+        n = len(jpegs)
+        t = self._table(table, channels)
+        srcs, ja = self._ptrs(jpegs)
+        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
+        ms = ctypes.c_float(0)
+        st = (ctypes.c_float * 8)()
+        self._check(self._lib.vf_jpeg_bench_lut(self._ctx, ja, js, n, t.ctypes.data, channels, quality, subsamp,
+                                                flags, iters, ctypes.byref(ms), st))
+        names = ("unstuff", "huffman_sync", "huffman_write", "dc_idct", "color_lut", "fdct_huffman",
                  "stuffing", "sync_passes")
         return ms.value, dict(zip(names, [float(x) for x in st]))
 

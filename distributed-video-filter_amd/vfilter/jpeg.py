@@ -27,6 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
+from .filters import as_table
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -114,6 +115,32 @@ class TurboJPEG:
         """``invert_batch_submit`` for JPEGs given by address and size arrays (a worker's ring
         slots; the memory stays valid until the result is collected)."""
         return self.ctx.jpeg_invert_submit_addrs(addrs, sizes, quality, jpeg_subsample, self._enc_flags(flags, quality))
+
+    # -- any other per-pixel filter: a 256-entry table (cv2.LUT) between decode and encode ----------
+    def lut(self, jpeg_buf, table, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(cv2.LUT(decode(jpeg_buf), table))`` fused on the GPU.  ``table`` as for
+        ``vfilter.lut``; a 3-channel table's channel c is channel c of the decoded BGR frame."""
+        return self.lut_batch([jpeg_buf], table, quality, jpeg_subsample, flags)[0]
+
+    def lut_batch(self, jpeg_bufs: Sequence, table, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                  flags: int = 0) -> List[bytes]:
+        planar, channels = as_table(table)
+        return self.ctx.jpeg_lut(list(jpeg_bufs), planar, channels, quality, jpeg_subsample,
+                                 self._enc_flags(flags, quality))
+
+    def lut_batch_submit(self, jpeg_bufs: Sequence, table, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                         flags: int = 0) -> int:
+        """lut_batch, asynchronously; the ticket is collected with the ``invert_batch_result*``
+        methods (the table is copied: the caller may change it at once)."""
+        planar, channels = as_table(table)
+        return self.ctx.jpeg_lut_submit(list(jpeg_bufs), planar, channels, quality, jpeg_subsample,
+                                        self._enc_flags(flags, quality))
+
+    def lut_batch_submit_addrs(self, addrs, sizes, table, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                               flags: int = 0) -> int:
+        planar, channels = as_table(table)
+        return self.ctx.jpeg_lut_submit_addrs(addrs, sizes, planar, channels, quality, jpeg_subsample,
+                                              self._enc_flags(flags, quality))
 
     def invert_batch_result_into_addrs(self, ticket: int, out_addrs, cap: int):
         """(sizes, {i: JPEG that did not fit}): each result written at ``out_addrs[i]`` (``cap``

@@ -294,6 +294,47 @@ int vf_jpeg_invert_scatter(vf_ctx *ctx, uint64_t ticket, uint8_t *const *outs, c
 int vf_jpeg_bench_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                          int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms);
 
+/* ---- another filter: a 256-entry table per channel (cv2.LUT) --------------------------
+ *
+ * Every per-pixel filter a plugin may put where the reference has cv2.bitwise_not
+ * (inverter.py:41) -- gamma, levels, threshold, posterize, per-channel curves -- is
+ * cv2.LUT(frame, table).  One table convention everywhere: `table` is channels x 256 bytes,
+ * planar, table[c * 256 + v] = the output of value v in channel c, channels 1 or 3.  With one
+ * channel every byte goes through the one table; with three the data is interleaved 3-channel,
+ * a frame starts at channel 0 and its byte i uses table i % 3.  On the JPEG path channel c is
+ * channel c of the decoded BGR pixel (inverter.py:32), so table[0..255] is applied to B.
+ * `table` is a HOST pointer, read during the call only.  A NULL table, any other `channels`, or
+ * (channels == 3) a frame whose size is not a multiple of 3 is VF_E_INVALID. */
+
+/* Enqueue the table kernel on `stream` over device memory, the frame starting at channel 0.
+ * Returns after the launch (does not synchronise); any alignment; dsrc == ddst is allowed. */
+int vf_lut_device(vf_ctx *ctx, const void *dsrc, void *ddst, size_t nbytes,
+                  const uint8_t *table, int channels, void *stream);
+
+/* The filter on `n` separately allocated host frames (srcs[i] -> dsts[i], nbytes[i] each),
+ * synchronous: upload, kernel, download on a stream of the context.  Pageable or page-locked
+ * memory at any alignment, srcs[i] == dsts[i] allowed, frames independent as for
+ * vf_invert_frames_host.  Frames larger than the context's staging are cut (mid-pixel if need
+ * be).  Not pipelined: the zero-copy and asynchronous paths are vf_invert_*'s alone. */
+int vf_lut_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                       const size_t *nbytes, int n, const uint8_t *table, int channels);
+
+/* vf_jpeg_invert with the table in place of the inversion: decode -> cv2.LUT -> encode. */
+int vf_jpeg_lut(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                const uint8_t *table, int channels, int quality, int subsamp, int flags,
+                uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the table (copied: the caller may reuse it at once).  The ticket
+ * is an invert ticket: collect with vf_jpeg_invert_query / _wait / _fetch / _scatter. */
+int vf_jpeg_lut_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                       const uint8_t *table, int channels, int quality, int subsamp, int flags,
+                       uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the table in the colour stage. */
+int vf_jpeg_bench_lut(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                      const uint8_t *table, int channels, int quality, int subsamp, int flags,
+                      int iters, float *ms, float *stage_ms);
+
 #ifdef __cplusplus
 }
 #endif
