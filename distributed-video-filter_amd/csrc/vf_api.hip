@@ -33,6 +33,8 @@
 #include "vf_internal.h"
 #include "vf_jpeg_codec.h"
 #include "vf_lut_split.h"
+#include "vf_conv_bands.h"
+#include "vf_conv_border.h"
 
 #define VF_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -461,6 +463,138 @@ VF_EXPORT int vf_lut_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_
   return VF_OK;
 }
 
+// ---- 2-D convolution filter (cv2.filter2D) on raw frames ---------------------------------------
+
+namespace {
+
+// The kernel arguments every vf_conv_* / vf_jpeg_conv* entry point shares.
+int check_kernel(vf_ctx *ctx, const char *fn, const int16_t *weights, int kw, int kh, int shift, int border) {
+  if (!weights) return set_err(ctx, VF_E_INVALID, 0, "%s: weights is NULL", fn);
+  if (kw < 1 || kh < 1 || kw > vf::conv::kMaxK || kh > vf::conv::kMaxK || !(kw & 1) || !(kh & 1))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: a %d x %d kernel; sides are odd and at most %d", fn, kw, kh,
+                   vf::conv::kMaxK);
+  if (shift < 0 || shift > 16) return set_err(ctx, VF_E_INVALID, 0, "%s: shift=%d outside 0..16", fn, shift);
+  long sum = 0;
+  for (int i = 0; i < kw * kh; ++i) sum += std::labs((long)weights[i]);
+  if (sum > 65536) return set_err(ctx, VF_E_INVALID, 0, "%s: sum|K| = %ld exceeds 65536", fn, sum);
+  if (border != VF_BORDER_REFLECT101 && border != VF_BORDER_REPLICATE && border != VF_BORDER_CONSTANT)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: unknown border %d", fn, border);
+  return VF_OK;
+}
+
+int check_frame_shape(vf_ctx *ctx, const char *fn, int width, int height, int channels) {
+  if (width <= 0 || height <= 0)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: a %d x %d frame", fn, width, height);
+  if ((uint64_t)width * (uint64_t)channels > 0x7FFFFFFFull)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: rows of %d pixels are too long", fn, width);
+  return VF_OK;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_conv_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                             const int16_t *weights, int kw, int kh, int shift, int border, void *stream) {
+  VF_CHECK_CTX(ctx);
+  int rc = check_kernel(ctx, "vf_conv_device", weights, kw, kh, shift, border);
+  if (rc != VF_OK) return rc;
+  if (channels != 1 && channels != 3)
+    return set_err(ctx, VF_E_INVALID, 0, "vf_conv_device: channels=%d, a frame has 1 or 3", channels);
+  if (width == 0 && height == 0) return VF_OK;  // the empty frame
+  if ((rc = check_frame_shape(ctx, "vf_conv_device", width, height, channels)) != VF_OK) return rc;
+  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "vf_conv_device: NULL buffer");
+  const size_t nbytes = (size_t)width * (size_t)channels * (size_t)height;
+  const uint8_t *s = (const uint8_t *)dsrc, *d = (const uint8_t *)ddst;
+  if (s < d + nbytes && d < s + nbytes)  // out of place only: a tap reads what a neighbour writes
+    return set_err(ctx, VF_E_INVALID, 0, "vf_conv_device: src and dst overlap");
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, vf::launch_conv(dsrc, ddst, width, channels, height, 0, height, 0, height, weights, kw, kh, shift, border,
+                              vf::conv_form_env(), (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                  const int *heights, int n, int channels, const int16_t *weights, int kw, int kh,
+                                  int shift, int border) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_conv_frames_host";
+  int rc = check_kernel(ctx, fn, weights, kw, kh, shift, border);
+  if (rc != VF_OK) return rc;
+  if (channels != 1 && channels != 3)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: channels=%d, a frame has 1 or 3", fn, channels);
+  if (n < 0) return set_err(ctx, VF_E_INVALID, 0, "%s: n < 0", fn);
+  if (n > 0 && (!srcs || !dsts || !widths || !heights)) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL array", fn);
+  // one upload + launch + download per band (vf_conv_bands.h); most frames are one band
+  struct Piece {
+    int frame;
+    vf::conv::Band b;
+    const uint8_t *halo;  // in-place frames: the band's rows [s0, y0), saved before a download overwrote them
+  };
+  std::vector<Piece> pieces;
+  std::vector<std::vector<uint8_t>> saved;
+  const size_t cap = ctx->lut_cap;
+  const int ry = kh / 2;
+  for (int i = 0; i < n; ++i) {
+    if (widths[i] == 0 && heights[i] == 0) continue;  // the empty frame
+    if ((rc = check_frame_shape(ctx, fn, widths[i], heights[i], channels)) != VF_OK) return rc;
+    if (!srcs[i] || !dsts[i]) return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d has a NULL buffer", fn, i);
+    const size_t row = (size_t)widths[i] * (size_t)channels;
+    if (overlaps_partially(srcs[i], dsts[i], row * (size_t)heights[i]))
+      return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d src/dst partially overlap", fn, i);
+    std::vector<vf::conv::Band> bs;
+    if (!vf::conv::bands(widths[i], heights[i], channels, ry, cap, &bs))
+      return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %d rows of %zu bytes do not fit the context's %zu-byte staging",
+                     fn, i, 2 * ry + 1, row, cap);
+    for (const vf::conv::Band &b : bs) {
+      const uint8_t *halo = nullptr;
+      if (srcs[i] == dsts[i] && b.s0 < b.y0) {  // these rows are output rows of the band before
+        saved.emplace_back(srcs[i] + (size_t)b.s0 * row, srcs[i] + (size_t)b.y0 * row);
+        halo = saved.back().data();
+      }
+      pieces.push_back(Piece{i, b, halo});
+    }
+  }
+  if (pieces.empty()) return VF_OK;
+  std::lock_guard<std::mutex> lk(ctx->lut_mu);
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t alloc = ((cap + 15 + 15) & ~(size_t)15);
+  if ((rc = lut_staging(ctx, alloc)) != VF_OK) return rc;
+  hipStream_t st = ctx->lut_stream;
+  const int form = vf::conv_form_env();
+  std::vector<size_t> at(pieces.size());
+  for (size_t i = 0; i < pieces.size();) {
+    // one fill of the buffers: upload and filter the bands that fit, download them, wait
+    size_t cin = 0, cout = 0, j = i;
+    for (; j < pieces.size(); ++j) {
+      const Piece &p = pieces[j];
+      const size_t row = (size_t)widths[p.frame] * (size_t)channels;
+      const size_t in_bytes = (size_t)(p.b.s1 - p.b.s0) * row, out_bytes = (size_t)(p.b.y1 - p.b.y0) * row;
+      if (cin + in_bytes > alloc || cout + out_bytes > alloc) break;
+      uint8_t *din = ctx->lut_din + cin, *dout = ctx->lut_dout + cout;
+      const uint8_t *src = srcs[p.frame];
+      size_t head = 0;
+      if (p.halo) {
+        head = (size_t)(p.b.y0 - p.b.s0) * row;
+        VF_HIP(ctx, hipMemcpyAsync(din, p.halo, head, hipMemcpyHostToDevice, st));
+      }
+      VF_HIP(ctx, hipMemcpyAsync(din + head, src + (size_t)p.b.s0 * row + head, in_bytes - head, hipMemcpyHostToDevice, st));
+      VF_HIP(ctx, vf::launch_conv(din, dout, widths[p.frame], channels, heights[p.frame], p.b.y0, p.b.y1 - p.b.y0, p.b.s0,
+                                  p.b.s1 - p.b.s0, weights, kw, kh, shift, border, form, st));
+      at[j] = cout;
+      cin += (in_bytes + 15) & ~(size_t)15;
+      cout += (out_bytes + 15) & ~(size_t)15;
+    }
+    for (size_t k = i; k < j; ++k) {
+      const Piece &p = pieces[k];
+      const size_t row = (size_t)widths[p.frame] * (size_t)channels;
+      VF_HIP(ctx, hipMemcpyAsync(dsts[p.frame] + (size_t)p.b.y0 * row, ctx->lut_dout + at[k],
+                                 (size_t)(p.b.y1 - p.b.y0) * row, hipMemcpyDeviceToHost, st));
+    }
+    VF_HIP(ctx, hipStreamSynchronize(st));
+    i = j;
+  }
+  return VF_OK;
+}
+
 // ---- memory helpers ------------------------------------------------------------------------
 
 VF_EXPORT int vf_alloc_device(vf_ctx *ctx, size_t nbytes, void **out) {
@@ -793,7 +927,7 @@ namespace {
 // decode -> filter -> encode for vf_jpeg_invert (lut == nullptr: bitwise_not) and vf_jpeg_lut
 int jpeg_filter(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
                 int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes, const uint8_t *lut,
-                int channels) {
+                int channels, const vf::jpeg::ConvSpec *conv = nullptr) {
   if (n < 0 || (n > 0 && (!jpegs || !jpeg_sizes || !outs || !caps || !sizes)))
     return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
   if (n > 65535) return set_err(ctx, VF_E_INVALID, 0, "%s: at most 65535 frames per call", fn);
@@ -802,12 +936,13 @@ int jpeg_filter(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const 
   int rc = jpeg_codec(ctx, lease, &c);
   if (rc) return rc;
   std::string err;
-  rc = c->invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, &err, lut, channels);
+  rc = c->invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, &err, lut, channels, conv);
   return jpeg_status(ctx, rc, std::string(fn) + ": " + err);
 }
 
 int jpeg_filter_submit(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
-                       int quality, int subsamp, int flags, uint64_t *ticket, const uint8_t *lut, int channels) {
+                       int quality, int subsamp, int flags, uint64_t *ticket, const uint8_t *lut, int channels,
+                       const vf::jpeg::ConvSpec *conv = nullptr) {
   if (!ticket || n <= 0 || n > 65535 || !jpegs || !jpeg_sizes)
     return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
   *ticket = 0;
@@ -815,7 +950,7 @@ int jpeg_filter_submit(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs,
   if (!c)
     return set_err(ctx, VF_E_INVALID, 0, "%s: %zu batches already in flight; fetch one first", fn, kMaxJpegJobs);
   std::string err;
-  const int rc = c->submit_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, &err, lut, channels);
+  const int rc = c->submit_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, &err, lut, channels, conv);
   if (rc != VF_OK) {
     c->quiesce();  // a submit that failed after queueing work must not hand the codec on mid-flight
     give_back(ctx, c);
@@ -829,7 +964,7 @@ int jpeg_filter_submit(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs,
 
 int jpeg_filter_bench(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                       int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms, const uint8_t *lut,
-                      int channels) {
+                      int channels, const vf::jpeg::ConvSpec *conv = nullptr) {
   if (n <= 0 || n > 65535 || !jpegs || !jpeg_sizes || !ms || iters <= 0)
     return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
   CodecLease lease(ctx);
@@ -837,8 +972,22 @@ int jpeg_filter_bench(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, 
   int rc = jpeg_codec(ctx, lease, &c);
   if (rc) return rc;
   std::string err;
-  rc = c->bench_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms, &err, lut, channels);
+  rc = c->bench_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms, &err, lut, channels, conv);
   return jpeg_status(ctx, rc, std::string(fn) + ": " + err);
+}
+
+// the checked kernel of a vf_jpeg_conv* call as the codec takes it
+int conv_spec(vf_ctx *ctx, const char *fn, const int16_t *weights, int kw, int kh, int shift, int border,
+              vf::jpeg::ConvSpec *out) {
+  const int rc = check_kernel(ctx, fn, weights, kw, kh, shift, border);
+  if (rc != VF_OK) return rc;
+  std::memset(out, 0, sizeof *out);
+  std::memcpy(out->w, weights, sizeof(int16_t) * (size_t)(kw * kh));
+  out->kw = kw;
+  out->kh = kh;
+  out->shift = shift;
+  out->border = border;
+  return VF_OK;
 }
 
 }  // namespace
@@ -939,4 +1088,37 @@ VF_EXPORT int vf_jpeg_bench_lut(vf_ctx *ctx, const uint8_t *const *jpegs, const 
   if (rc != VF_OK) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_lut", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
                            table, channels);
+}
+
+VF_EXPORT int vf_jpeg_conv(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                           const int16_t *weights, int kw, int kh, int shift, int border, int quality, int subsamp,
+                           int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  vf::jpeg::ConvSpec spec;
+  const int rc = conv_spec(ctx, "vf_jpeg_conv", weights, kw, kh, shift, border, &spec);
+  if (rc != VF_OK) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_conv", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, nullptr, 0,
+                     &spec);
+}
+
+VF_EXPORT int vf_jpeg_conv_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                  const int16_t *weights, int kw, int kh, int shift, int border, int quality,
+                                  int subsamp, int flags, uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  vf::jpeg::ConvSpec spec;
+  const int rc = conv_spec(ctx, "vf_jpeg_conv_submit", weights, kw, kh, shift, border, &spec);
+  if (rc != VF_OK) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_conv_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, nullptr,
+                            0, &spec);
+}
+
+VF_EXPORT int vf_jpeg_bench_conv(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                 const int16_t *weights, int kw, int kh, int shift, int border, int quality,
+                                 int subsamp, int flags, int iters, float *ms, float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  vf::jpeg::ConvSpec spec;
+  const int rc = conv_spec(ctx, "vf_jpeg_bench_conv", weights, kw, kh, shift, border, &spec);
+  if (rc != VF_OK) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_conv", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
+                           stage_ms, nullptr, 0, &spec);
 }

@@ -37,6 +37,21 @@ hipError_t launch_invert_frames(const void *const *dsrcs, void *const *ddsts,
 hipError_t launch_lut(const void *dsrc, void *ddst, size_t nbytes, const uint8_t *table, int channels,
                       uint32_t phase, const LaunchCfg &cfg, hipStream_t stream);
 
+// The 2-D convolution filter (vf_conv.hip), out of place, on packed rows of width * channels
+// bytes.  Output rows [y0, y0 + nrows) of a frame of frame_h rows go to ddst (row y0 first); dsrc
+// holds the frame's rows [s0, s0 + nsrc) (row s0 first), which must cover every row a tap of
+// those output rows resolves to (vf_conv_bands.h); a whole frame is y0 = s0 = 0, nrows = nsrc =
+// frame_h.  weights: kw * kh int16 in HOST memory, row-major, passed on by value.  border: a
+// conv::k* of vf_conv_border.h.  form: 0 the narrow arithmetic form when it holds the kernel, 1
+// always the wide one, 2 as 0 (conv_form_env reads VF_CONV_FORM = wide | narrow).
+constexpr int kConvTileBytes = 256;  // a workgroup's output tile: row bytes ...
+constexpr int kConvTileRows = 16;    // ... x rows
+hipError_t launch_conv(const void *dsrc, void *ddst, int width, int channels, int frame_h, int y0, int nrows, int s0,
+                       int nsrc, const int16_t *weights, int kw, int kh, int shift, int border, int form,
+                       hipStream_t stream);
+bool conv_narrow_fits(const int16_t *weights, int count);  // sum|K| * 255 < 2^15
+int conv_form_env();
+
 // Up to kMappedMax page-locked host ranges, by their device addresses, inverted in place over
 // PCIe by one launch (vf_kernels.hip invert_mapped_kernel; passed by value as kernel arguments).
 constexpr int kMappedMax = 64;

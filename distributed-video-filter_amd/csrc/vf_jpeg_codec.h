@@ -90,6 +90,13 @@ struct ComputeGate {
   hipEvent_t last = nullptr;
 };
 
+// The 2-D convolution filter of a batch (vf_jpeg_conv*): kw x kh integer weights, row-major, the
+// result shifted right by `shift` with round-half-even, `border` a VF_BORDER_* (DESIGN.md 16).
+struct ConvSpec {
+  int16_t w[49];
+  int kw, kh, shift, border;
+};
+
 int header_info(const uint8_t *jpeg, size_t size, int *w, int *h, int *subsamp, int *colorspace, std::string *err);
 size_t buffer_size(int w, int h, int subsamp);
 
@@ -109,13 +116,16 @@ class Codec {
   // applied to the decoded BGR pixels in place of the inversion (cv2.LUT); read during the call
   int invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
              uint8_t *const *outs, const size_t *caps, size_t *out_sizes, std::string *err,
-             const uint8_t *lut = nullptr, int channels = 0);
+             const uint8_t *lut = nullptr, int channels = 0, const ConvSpec *conv = nullptr);
+  // conv (here and in submit_invert, bench_invert; copied): cv2.filter2D on the decoded BGR pixels in
+  // place of the inversion, through the unfused pixel round trip: decode into d_pix_, the
+  // convolution kernel per frame into d_pix2_, which the encoder reads
   // invert() in three steps, so one host thread can keep batches of two codecs in flight:
   // submit_invert returns once everything is queued (inputs staged: the caller's buffers may go);
   // done_invert never blocks; wait_invert blocks and gives the packed output size; fetch_invert
   // copies the packed outputs (frame f at offs[f], sizes[f] bytes; out may be NULL).
   int submit_invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
-                    std::string *err, const uint8_t *lut = nullptr, int channels = 0);
+                    std::string *err, const uint8_t *lut = nullptr, int channels = 0, const ConvSpec *conv = nullptr);
   bool done_invert();
   int wait_invert(size_t *total, std::string *err);
   int fetch_invert(uint8_t *out, size_t cap, size_t *sizes, size_t *offs, std::string *err);
@@ -133,7 +143,7 @@ class Codec {
   // stage_ms[0..6] = unstuff, sync, write, dc+idct, colour, fdct+huffman, stuffing; [7] = passes
   int bench_invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
                    int iters, float *ms, float *stage_ms, std::string *err, const uint8_t *lut = nullptr,
-                   int channels = 0);
+                   int channels = 0, const ConvSpec *conv = nullptr);
 
  private:
   int init(std::string *err);
@@ -149,7 +159,10 @@ class Codec {
   int settle_decode(int bgr, bool invert, Tail &&tail, std::string *err);
   int prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs, int n, int quality, int subsamp,
                      bool fastdct, std::string *err);
-  int run_encode(int bgr, bool fastdct, std::string *err);
+  // pix: the BGR / RGB pixels the encoder reads when the plan is not fused (d_pix_ or d_pix2_)
+  int run_encode(int bgr, bool fastdct, const uint8_t *pix, std::string *err);
+  // what the invert path queues behind its decode: the convolution, if the batch has one, and the encode
+  int run_filter_encode(bool fastdct, std::string *err);
   int queue_fetch(uint64_t guess, std::string *err);
   int finish_fetch(std::string *err);
   int copy_out(uint8_t *const *outs, const size_t *caps, size_t *sizes, std::string *err);
@@ -193,6 +206,9 @@ class Codec {
   DevBuf d_eplanes_;  // the invert path's encoder sample planes (plan_.fuse)
   bool has_lut_ = false;  // the invert path's filter is lut_ (else the inversion)
   LutTable lut_ = {};
+  bool has_conv_ = false;  // the invert path's filter is conv_, applied between decode and encode
+  ConvSpec conv_ = {};
+  DevBuf d_pix2_;  // the convolution's output: the batch's frames at their d_pix_ offsets
   int dcm_ = -1;  // k_color layout shared by the batch's frames (1..3, 0 general), -1 mixed
   DevBuf d_efr_, d_etab_, d_hdr_, d_esegs_, d_etsum_, d_etotals_, d_dcq_, d_acbits_, d_acscr_, d_bits_, d_pre_, d_bitoff_, d_stream_, d_ffcnt_,
       d_outsize_, d_pack_;

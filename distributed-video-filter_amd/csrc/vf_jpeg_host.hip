@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "vf_host_mem.h"
+#include "vf_internal.h"
 #include "vf_jpeg.h"
 #include "vf_jpeg_codec.h"
 #include "vf_jpeg_parse.h"
@@ -870,14 +871,29 @@ int Codec::prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs
   return kOk;
 }
 
-int Codec::run_encode(int bgr, bool fastdct, std::string *err) {
+// The invert path's tail behind the decode.  With a convolution the decode left plain BGR pixels
+// in d_pix_ (the plan is not fused); each frame goes through the raw kernel (vf_conv.hip) into
+// d_pix2_ at the same offset and the encoder reads that.  settle_decode's tails call this, so a
+// batch resynchronised at wait_invert is filtered again from freshly decoded pixels: once.
+int Codec::run_filter_encode(bool fastdct, std::string *err) {
+  if (!has_conv_) return run_encode(1, fastdct, d_pix_.as<uint8_t>(), err);
+  CK(d_pix2_.ensure(dpix_bytes_));
+  for (int f = 0; f < dn_; ++f) {
+    const DecFrame &F = dfr_[(size_t)f];
+    CK(launch_conv(d_pix_.as<uint8_t>() + F.out_off, d_pix2_.as<uint8_t>() + F.out_off, F.g.w, 3, F.g.h, 0, F.g.h, 0,
+                   F.g.h, conv_.w, conv_.kw, conv_.kh, conv_.shift, conv_.border, 0, s_));
+  }
+  return run_encode(1, fastdct, d_pix2_.as<uint8_t>(), err);
+}
+
+int Codec::run_encode(int bgr, bool fastdct, const uint8_t *pix, std::string *err) {
   const EncFrame *fr = d_efr_.as<EncFrame>();
   const EncTables *tab = d_etab_.as<EncTables>();
   const ScanSeg *segs = d_esegs_.as<ScanSeg>();
   const int n = en_;
   const bool fuse = plan_.fuse;  // the decoder's colour pass wrote the sample planes
   CK(stage_event(6));
-  CK(enc_fdct(fr, n, emax_blocks_, tab, fuse ? d_eplanes_.as<uint8_t>() : d_pix_.as<uint8_t>(), d_dcq_.as<int16_t>(),
+  CK(enc_fdct(fr, n, emax_blocks_, tab, fuse ? d_eplanes_.as<uint8_t>() : pix, d_dcq_.as<int16_t>(),
               d_acbits_.as<uint32_t>(), d_acscr_.as<uint32_t>(), bgr, fastdct ? 1 : 0, kSampH[esub_], kSampV[esub_],
               fuse ? 1 : 0, s_));
   CK(enc_len(fr, n, emax_blocks_, tab, d_dcq_.as<int16_t>(), d_acbits_.as<uint32_t>(), d_bits_.as<uint32_t>(),
@@ -982,13 +998,14 @@ int Codec::encode(const uint8_t *const *imgs, const int *ws, const int *hs, int 
   const bool fast = (flags & kFlagFastDct) != 0;
   if ((rc = prepare_encode(ws, hs, offs.data(), n, quality, subsamp, fast, err))) return rc;
   plan_ = DecodePlan();  // no decode, no switches: run_encode reads pixels (plan_.fuse off)
+  has_conv_ = false;
   CK(h_stage_.ensure(pix));
   CK(d_pix_.ensure(pix));
   pool_.run(n, [&](int f) {
     std::memcpy(h_stage_.as<uint8_t>() + offs[(size_t)f], imgs[f], (size_t)ws[f] * hs[f] * 3);
   });
   CK(hipMemcpyAsync(d_pix_.p, h_stage_.p, pix, hipMemcpyHostToDevice, s_));
-  if ((rc = run_encode(pixel_format, fast, err))) return rc;
+  if ((rc = run_encode(pixel_format, fast, d_pix_.as<uint8_t>(), err))) return rc;
   uint64_t guess = 0;
   for (int f = 0; f < n; ++f) guess += align_up((size_t)ws[f] * hs[f] / 4 + 8192, 64);
   if ((rc = queue_fetch(guess, err))) return rc;
@@ -1067,11 +1084,14 @@ int Codec::set_filter(const uint8_t *lut, int channels, std::string *err) {
 }
 
 int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp,
-                         int flags, std::string *err, const uint8_t *lut, int channels) {
+                         int flags, std::string *err, const uint8_t *lut, int channels, const ConvSpec *conv) {
   int rc = init(err);
   if (rc) return rc;
   waited_ = false;
   if ((rc = set_filter(lut, channels, err))) return rc;
+  has_conv_ = conv != nullptr;
+  if (conv) conv_ = *conv;
+  const bool inv = !has_conv_;  // the colour stage filters (inversion or table); else plain pixels for the convolution
   if (n <= 0) {
     *err = "empty batch";
     return kInvalid;
@@ -1079,7 +1099,7 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
   const JpegSwitches sw = JpegSwitches::read();
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
-  if ((rc = prepare_decode(jpegs, jsizes, n, flags, sw, true, err))) return rc;
+  if ((rc = prepare_decode(jpegs, jsizes, n, flags, sw, inv, err))) return rc;
   const auto t1 = clk::now();
   std::vector<int> ws((size_t)n), hs((size_t)n);
   std::vector<uint64_t> offs((size_t)n);
@@ -1108,8 +1128,8 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
       if (gate_->last) CK(hipStreamWaitEvent(s_, gate_->last, 0));
     }
     // decode (BGR, inverted: cv2.bitwise_not, inverter.py:41) straight into the encoder's input
-    if ((rc = run_decode(1, true, err))) return rc;
-    if ((rc = run_encode(1, plan_.enc_fast, err))) return rc;
+    if ((rc = run_decode(1, inv, err))) return rc;
+    if ((rc = run_filter_encode(plan_.enc_fast, err))) return rc;
     if (gate_) {
       CK(hipEventRecord(ev_[9], s_));
       gate_->last = ev_[9];
@@ -1146,8 +1166,8 @@ int Codec::wait_invert(size_t *total, std::string *err) {
   CK(hipEventSynchronize(done_));
   // everything from here on follows the plan submit_invert left: this may run on another thread,
   // under another environment
-  int rc = settle_decode(1, true, [&]() -> int {
-    int r = run_encode(1, plan_.enc_fast, err);
+  int rc = settle_decode(1, !has_conv_, [&]() -> int {
+    int r = run_filter_encode(plan_.enc_fast, err);
     if (!r) r = queue_fetch(guess_, err);
     if (r) return r;
     CK(hipEventSynchronize(done_));
@@ -1205,9 +1225,9 @@ int Codec::fetch_invert(uint8_t *out, size_t cap, size_t *sizes, size_t *offs, s
 
 int Codec::invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp, int flags,
                   uint8_t *const *outs, const size_t *caps, size_t *sizes, std::string *err, const uint8_t *lut,
-                  int channels) {
+                  int channels, const ConvSpec *conv) {
   if (n <= 0) return init(err);
-  int rc = submit_invert(jpegs, jsizes, n, quality, subsamp, flags, err, lut, channels);
+  int rc = submit_invert(jpegs, jsizes, n, quality, subsamp, flags, err, lut, channels, conv);
   size_t total = 0;
   if (!rc) rc = wait_invert(&total, err);
   if (!rc) rc = copy_out(outs, caps, sizes, err);
@@ -1216,7 +1236,7 @@ int Codec::invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
 
 int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp,
                         int flags, int iters, float *ms, float *stage_ms, std::string *err, const uint8_t *lut,
-                        int channels) {
+                        int channels, const ConvSpec *conv) {
   int rc = init(err);
   if (rc) return rc;
   if (n <= 0 || iters <= 0) {
@@ -1224,7 +1244,10 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
     return kInvalid;
   }
   if ((rc = set_filter(lut, channels, err))) return rc;
-  if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), true, err))) return rc;
+  has_conv_ = conv != nullptr;
+  if (conv) conv_ = *conv;
+  const bool inv = !has_conv_;
+  if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), inv, err))) return rc;
   std::vector<int> ws((size_t)n), hs((size_t)n);
   std::vector<uint64_t> offs((size_t)n);
   for (int f = 0; f < n; ++f) {
@@ -1245,7 +1268,7 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
     for (int it = 0; it < iters; ++it) {
       CK(hipStreamSynchronize(s_));
       const auto t0 = std::chrono::steady_clock::now();
-      if ((rc = run_decode(1, true, err)) || (rc = run_encode(1, fast, err))) {
+      if ((rc = run_decode(1, inv, err)) || (rc = run_filter_encode(fast, err))) {
         stage_events_ = false;
         return rc;
       }
@@ -1265,8 +1288,8 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
   }
   stage_events_ = false;
   CK(hipStreamSynchronize(s_));
-  rc = settle_decode(1, true, [&]() -> int {
-    const int r = run_encode(1, fast, err);
+  rc = settle_decode(1, inv, [&]() -> int {
+    const int r = run_filter_encode(fast, err);
     if (r) return r;
     CK(hipStreamSynchronize(s_));
     return kOk;

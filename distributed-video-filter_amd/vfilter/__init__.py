@@ -4,20 +4,23 @@ distributor.py).
 
   filters      ``bitwise_not`` (the ``cv2.bitwise_not`` drop-in, inverter.py:41) and batch forms;
                ``lut`` (the ``cv2.LUT`` drop-in: any other per-pixel filter) and ``lut_frames``
+               ``filter2d`` (the ``cv2.filter2D`` drop-in: blur, sharpen, Sobel, ...) and
+               ``filter2d_frames``
   tables       builders of the usual 256-entry tables (gamma, levels, threshold, posterize, ...)
+  kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
   _lib         ctypes binding to libvfilter_hip.so (include/vfilter.h)
 
 The worker loop, the inverter plugin and the distributor live in ``worker``,
 ``inverter`` and ``distributor`` (imported on demand; they need no GPU to import).
 """
-from . import tables  # noqa: F401
+from . import kernels, tables  # noqa: F401
 from ._lib import (ABI_VERSION, Context, VFilterError, device_count, get_context,  # noqa: F401
                    library_path, load_library)
-from .filters import (as_table, bitwise_not, invert, invert_batch, invert_bytes, invert_frames,  # noqa: F401
-                      lut, lut_frames)
+from .filters import (as_kernel, as_table, bitwise_not, filter2d, filter2d_frames, invert,  # noqa: F401
+                      invert_batch, invert_bytes, invert_frames, lut, lut_frames)
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
     "load_library", "bitwise_not", "invert", "invert_batch", "invert_bytes", "invert_frames",
-    "as_table", "lut", "lut_frames",
+    "as_table", "lut", "lut_frames", "as_kernel", "filter2d", "filter2d_frames", "kernels", "tables",
 ]

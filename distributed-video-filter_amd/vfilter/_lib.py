@@ -91,6 +91,18 @@ SIGNATURES = {
                                           ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "vf_jpeg_bench_lut": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
+    "vf_conv_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "vf_conv_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vf_jpeg_conv": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_conv_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_conv": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          _c_float_p, _c_float_p]),
 }
 
 
@@ -393,6 +405,34 @@ class Context:
     def lut_device(self, dsrc: int, ddst: int, nbytes: int, table, channels: int, stream: int = 0) -> None:
         t = self._table(table, channels)
         self._check(self._lib.vf_lut_device(self._ctx, dsrc, ddst, nbytes, t.ctypes.data, channels, stream or None))
+
+    # -- 2-D convolution filter (cv2.filter2D): vf_conv_* ---------------------------------------
+    @staticmethod
+    def _weights(weights) -> np.ndarray:
+        """``weights`` (``filters.as_kernel``'s first result) as an array to point at."""
+        w = np.asarray(weights)
+        if w.dtype != np.int16 or w.ndim != 2 or not w.flags.c_contiguous:
+            raise ValueError("weights must be a C-contiguous kh x kw int16 array (see vfilter.as_kernel)")
+        return w
+
+    def conv_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                         channels: int, weights, shift: int, border: int = 0) -> None:
+        n = len(srcs)
+        if not (len(dsts) == n == len(widths) == len(heights)):
+            raise ValueError("srcs, dsts, widths and heights must have the same length")
+        w = self._weights(weights)
+        sa = (ctypes.c_void_p * n)(*[_addr(s) for s in srcs])
+        da = (ctypes.c_void_p * n)(*[_addr(d) for d in dsts])
+        wa = (ctypes.c_int * n)(*[int(v) for v in widths])
+        ha = (ctypes.c_int * n)(*[int(v) for v in heights])
+        self._check(self._lib.vf_conv_frames_host(self._ctx, sa, da, wa, ha, n, channels, w.ctypes.data, w.shape[1],
+                                                  w.shape[0], shift, border))
+
+    def conv_device(self, dsrc: int, ddst: int, width: int, height: int, channels: int, weights, shift: int,
+                    border: int = 0, stream: int = 0) -> None:
+        w = self._weights(weights)
+        self._check(self._lib.vf_conv_device(self._ctx, dsrc, ddst, width, height, channels, w.ctypes.data, w.shape[1],
+                                             w.shape[0], shift, border, stream or None))
 
     # -- host -> host, asynchronous (page-locked buffers) -----------------------------------
     def invert_frames_async(self, srcs: Sequence, dsts: Sequence, nbytes: Sequence[int]) -> int:
@@ -762,6 +802,61 @@ class Context:
         self._check(self._lib.vf_jpeg_bench_lut(self._ctx, ja, js, n, t.ctypes.data, channels, quality, subsamp,
                                                 flags, iters, ctypes.byref(ms), st))
         names = ("unstuff", "huffman_sync", "huffman_write", "dc_idct", "color_lut", "fdct_huffman",
+                 "stuffing", "sync_passes")
+        return ms.value, dict(zip(names, [float(x) for x in st]))
+
+    # -- JPEG with a convolution in place of the inversion (vf_jpeg_conv*); tickets are invert tickets ----
+    def jpeg_conv(self, jpegs: Sequence, weights, shift: int, border: int, quality: int, subsamp: int,
+                  flags: int = 0) -> list:
+        """decode -> cv2.filter2D -> encode for every JPEG on the GPU; returns bytes."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_conv_submit(jpegs, weights, shift, border, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_conv_submit(self, jpegs: Sequence, weights, shift: int, border: int, quality: int, subsamp: int,
+                         flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the kernel; collect with the ``jpeg_invert_result*`` methods."""
+        n = len(jpegs)
+        if n == 0:
+            raise ValueError("jpeg_conv_submit: empty batch")
+        w = self._weights(weights)
+        srcs, ja = self._ptrs(jpegs)
+        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
+        tk = ctypes.c_uint64(0)
+        self._check(self._lib.vf_jpeg_conv_submit(self._ctx, ja, js, n, w.ctypes.data, w.shape[1], w.shape[0], shift,
+                                                  border, quality, subsamp, flags, ctypes.byref(tk)))
+        self.__dict__.setdefault("_jpeg_n", {})[tk.value] = n
+        return tk.value
+
+    def jpeg_conv_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, weights, shift: int, border: int,
+                               quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_conv_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        a = np.ascontiguousarray(addrs, np.uint64)
+        z = np.ascontiguousarray(sizes, np.uint64)
+        n = len(a)
+        if n == 0 or len(z) != n:
+            raise ValueError("jpeg_conv_submit_addrs: empty batch or sizes of another length")
+        w = self._weights(weights)
+        tk = ctypes.c_uint64(0)
+        self._check(self._lib.vf_jpeg_conv_submit(self._ctx, a.ctypes.data, z.ctypes.data, n, w.ctypes.data, w.shape[1],
+                                                  w.shape[0], shift, border, quality, subsamp, flags, ctypes.byref(tk)))
+        self.__dict__.setdefault("_jpeg_n", {})[tk.value] = n
+        return tk.value
+
+    def jpeg_bench_conv(self, jpegs: Sequence, weights, shift: int, border: int, quality: int, subsamp: int,
+                        flags: int = 0, iters: int = 10):
+        """``jpeg_bench_invert`` with the convolution between the decode and the encode (its time is
+        in the total, not in a stage: it runs between the colour and the fdct stage events)."""
+        n = len(jpegs)
+        w = self._weights(weights)
+        srcs, ja = self._ptrs(jpegs)
+        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
+        ms = ctypes.c_float(0)
+        st = (ctypes.c_float * 8)()
+        self._check(self._lib.vf_jpeg_bench_conv(self._ctx, ja, js, n, w.ctypes.data, w.shape[1], w.shape[0], shift,
+                                                 border, quality, subsamp, flags, iters, ctypes.byref(ms), st))
+        names = ("unstuff", "huffman_sync", "huffman_write", "dc_idct", "color", "fdct_huffman",
                  "stuffing", "sync_passes")
         return ms.value, dict(zip(names, [float(x) for x in st]))
 

@@ -128,6 +128,125 @@ def lut_frames(frames: Sequence, table, outs: Optional[List] = None, ctx: Option
     return outs
 
 
+BORDERS = {"reflect101": 0, "replicate": 1, "constant": 2}  # VF_BORDER_* (include/vfilter.h)
+
+
+def border_code(border) -> int:
+    """``border`` ("reflect101", the default of cv2.filter2D; "replicate"; "constant", with the
+    constant 0) as the library's code."""
+    try:
+        return BORDERS[border]
+    except (KeyError, TypeError):
+        raise ValueError(f"filter2d: border must be one of {sorted(BORDERS)}, not {border!r}") from None
+
+
+def as_kernel(kernel) -> tuple:
+    """A ``cv2.filter2D`` kernel in the library's form: ``(int16 kh x kw weights, shift)``, meaning
+    ``weights / 2**shift``, with the smallest such shift.
+
+    ``kernel`` is a 2-D integer array (shift 0), a ``(weights, shift)`` pair (``vfilter.kernels``
+    builds those), or a 2-D floating-point array that is *dyadic*: ``kernel * 2**s`` is integral for
+    some s in 0..16.  Sides are odd and at most 7, ``0 <= shift <= 16`` and ``sum|weights| <= 65536``.
+    Anything else -- a 1/9 mean, a sampled Gaussian -- raises ``ValueError`` with the reason: there is
+    no floating-point kernel path."""
+    shift = 0
+    if isinstance(kernel, tuple) and len(kernel) == 2 and np.ndim(kernel[1]) == 0 and np.ndim(kernel[0]) == 2:
+        kernel, shift = kernel
+        if int(shift) != shift:
+            raise ValueError(f"filter2d: shift must be an integer, not {shift!r}")
+        shift = int(shift)
+        k = np.asarray(kernel)
+        if k.dtype.kind not in "iub":
+            if k.dtype.kind != "f" or not np.array_equal(k, np.rint(k)):
+                raise ValueError("filter2d: the weights of a (weights, shift) pair must be integers")
+    else:
+        k = np.asarray(kernel)
+    if k.ndim != 2 or k.size == 0:
+        raise ValueError(f"filter2d: a kernel is a 2-D array, not shape {k.shape}")
+    kh, kw = k.shape
+    if kh % 2 == 0 or kw % 2 == 0 or kh > 7 or kw > 7:
+        raise ValueError(f"filter2d: a {kh} x {kw} kernel; sides must be odd and at most 7")
+    if not 0 <= shift <= 16:
+        raise ValueError(f"filter2d: shift = {shift} outside 0..16")
+    if k.dtype.kind == "f" and not np.array_equal(k, np.rint(k)):
+        if not np.isfinite(k).all():
+            raise ValueError("filter2d: the kernel has a non-finite weight")
+        k = k.astype(np.float64)
+        for s in range(1, 17):
+            scaled = k * float(1 << s)  # exact: a power of two
+            if np.array_equal(scaled, np.rint(scaled)):
+                k, shift = scaled, s
+                break
+        else:
+            raise ValueError("filter2d: the kernel is not dyadic (no s in 0..16 makes kernel * 2**s integral); "
+                             "give integer weights and a shift")
+    elif k.dtype.kind not in "iubf":
+        raise ValueError(f"filter2d: a kernel of dtype {k.dtype}")
+    w = np.asarray(np.rint(k) if k.dtype.kind == "f" else k).astype(np.int64)
+    while shift > 0 and not (w & 1).any():  # the smallest shift
+        w >>= 1
+        shift -= 1
+    total = int(np.abs(w).sum())
+    if total > 65536:
+        raise ValueError(f"filter2d: sum|weights| = {total} exceeds 65536")
+    if w.size and (int(w.max()) > 32767 or int(w.min()) < -32768):
+        raise ValueError("filter2d: a weight does not fit 16 bits")
+    return np.ascontiguousarray(w, dtype=np.int16), shift
+
+
+def _conv_frame(name: str, a) -> np.ndarray:
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+        raise ValueError(f"{name}: frames must be uint8 ndarrays")
+    if a.ndim == 3 and a.shape[2] in (1, 3):
+        return a
+    if a.ndim == 2:
+        return a
+    raise ValueError(f"{name}: a frame is H x W or H x W x 3, not shape {a.shape}")
+
+
+def filter2d(src: np.ndarray, kernel, dst: Optional[np.ndarray] = None, border: str = "reflect101",
+             ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.filter2D(src, -1, kernel)`` on uint8 ``H x W`` or ``H x W x 3`` input
+    (correlation, anchor at the centre, ``borderType`` reflect-101 by default), exact for the
+    kernels ``as_kernel`` accepts.  ``dst`` as for ``lut``; it may not be ``src`` (the filter reads
+    neighbours).  ``vfilter.kernels`` builds the usual kernels."""
+    weights, shift = as_kernel(kernel)
+    code = border_code(border)
+    src = np.ascontiguousarray(_conv_frame("filter2d", src))
+    if dst is None:
+        dst = np.empty_like(src)
+    elif not isinstance(dst, np.ndarray) or dst.shape != src.shape or dst.dtype != src.dtype or not dst.flags.c_contiguous:
+        raise ValueError("filter2d: dst must be C-contiguous with src's shape and dtype")
+    channels = 1 if src.ndim == 2 else src.shape[2]
+    if src.size:
+        (ctx or get_context()).conv_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, weights, shift,
+                                                code)
+    return dst
+
+
+def filter2d_frames(frames: Sequence, kernel, outs: Optional[List] = None, border: str = "reflect101",
+                    ctx: Optional[Context] = None) -> List:
+    """``filter2d`` over separately stored frames of one channel count and mixed sizes in one call.
+    Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
+    weights, shift = as_kernel(kernel)
+    code = border_code(border)
+    srcs = [np.ascontiguousarray(_conv_frame("filter2d_frames", f)) for f in frames]
+    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
+    if len(chans) > 1:
+        raise ValueError("filter2d_frames: the frames of one call have one channel count")
+    if outs is None:
+        outs = [np.empty_like(s) for s in srcs]
+    elif len(outs) != len(srcs) or any(o.shape != s.shape or o.dtype != np.uint8 or not o.flags.c_contiguous
+                                       for o, s in zip(outs, srcs)):
+        raise ValueError("filter2d_frames: outs must be C-contiguous uint8 arrays of the frames' shapes")
+    live = [(s, o) for s, o in zip(srcs, outs) if s.size]
+    if live:
+        (ctx or get_context()).conv_frames_host([s for s, _ in live], [o for _, o in live],
+                                                [s.shape[1] for s, _ in live], [s.shape[0] for s, _ in live],
+                                                chans.pop(), weights, shift, code)
+    return outs
+
+
 def invert_frames(frames: Sequence, outs: Optional[List] = None,
                   ctx: Optional[Context] = None) -> List:
     """Invert separately stored frames (ndarrays or bytes-likes; mixed sizes allowed) with

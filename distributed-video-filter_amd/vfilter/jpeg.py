@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import as_table
+from .filters import as_kernel, as_table, border_code
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -141,6 +141,34 @@ class TurboJPEG:
         planar, channels = as_table(table)
         return self.ctx.jpeg_lut_submit_addrs(addrs, sizes, planar, channels, quality, jpeg_subsample,
                                               self._enc_flags(flags, quality))
+
+    # -- a neighbourhood filter: cv2.filter2D between decode and encode --------------------------------
+    def filter2d(self, jpeg_buf, kernel, border: str = "reflect101", quality: int = 85,
+                 jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(cv2.filter2D(decode(jpeg_buf), -1, kernel))`` on the GPU, the pixels never leaving
+        it.  ``kernel`` and ``border`` as for ``vfilter.filter2d``; the kernel is applied to each
+        channel of the decoded BGR frame."""
+        return self.filter2d_batch([jpeg_buf], kernel, border, quality, jpeg_subsample, flags)[0]
+
+    def filter2d_batch(self, jpeg_bufs: Sequence, kernel, border: str = "reflect101", quality: int = 85,
+                       jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        weights, shift = as_kernel(kernel)
+        return self.ctx.jpeg_conv(list(jpeg_bufs), weights, shift, border_code(border), quality, jpeg_subsample,
+                                  self._enc_flags(flags, quality))
+
+    def filter2d_batch_submit(self, jpeg_bufs: Sequence, kernel, border: str = "reflect101", quality: int = 85,
+                              jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> int:
+        """filter2d_batch, asynchronously; the ticket is collected with the ``invert_batch_result*``
+        methods (the kernel is copied: the caller may change it at once)."""
+        weights, shift = as_kernel(kernel)
+        return self.ctx.jpeg_conv_submit(list(jpeg_bufs), weights, shift, border_code(border), quality,
+                                         jpeg_subsample, self._enc_flags(flags, quality))
+
+    def filter2d_batch_submit_addrs(self, addrs, sizes, kernel, border: str = "reflect101", quality: int = 85,
+                                    jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> int:
+        weights, shift = as_kernel(kernel)
+        return self.ctx.jpeg_conv_submit_addrs(addrs, sizes, weights, shift, border_code(border), quality,
+                                               jpeg_subsample, self._enc_flags(flags, quality))
 
     def invert_batch_result_into_addrs(self, ticket: int, out_addrs, cap: int):
         """(sizes, {i: JPEG that did not fit}): each result written at ``out_addrs[i]`` (``cap``

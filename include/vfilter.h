@@ -335,6 +335,49 @@ int vf_jpeg_bench_lut(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jp
                       const uint8_t *table, int channels, int quality, int subsamp, int flags,
                       int iters, float *ms, float *stage_ms);
 
+/* ---- 2-D convolution filter (cv2.filter2D) ------------------------------------------------
+ * dst = cv2.filter2D(src, -1, K / 2^shift) for uint8 frames of 1 or 3 interleaved channels in
+ * packed rows: correlation (no flip), anchor at the centre, exact integer arithmetic, the sum
+ * rounded half to even and saturated to 0..255.  `weights` is a HOST pointer to
+ * kw * kh int16, row-major, read during the call only; kw and kh are odd and at most 7,
+ * 0 <= shift <= 16, sum|K| <= 65536.  `border` is one of VF_BORDER_*.  Anything else, a NULL
+ * `weights`, `channels` other than 1 or 3, or a frame with width <= 0 or height <= 0 (other than
+ * the empty 0 x 0 frame, which is skipped) is VF_E_INVALID. */
+#define VF_BORDER_REFLECT101 0 /* cv2.BORDER_DEFAULT: gfedcb|abcdefgh|gfedcba */
+#define VF_BORDER_REPLICATE  1 /* aaaaaa|abcdefgh|hhhhhhh */
+#define VF_BORDER_CONSTANT   2 /* 000000|abcdefgh|0000000 (the constant is 0) */
+
+/* Enqueue the convolution on `stream` over device memory (width * height * channels bytes
+ * each).  Returns after the launch (does not synchronise); any alignment.  Out of place only:
+ * ranges that overlap are VF_E_INVALID. */
+int vf_conv_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                   const int16_t *weights, int kw, int kh, int shift, int border, void *stream);
+
+/* The filter on `n` separately allocated host frames (srcs[i] -> dsts[i], widths[i] x heights[i]
+ * x channels), synchronous: upload, kernel, download on a stream of the context.  srcs[i] ==
+ * dsts[i] is allowed.  A frame larger than the context's staging is cut into bands of rows with
+ * their halo; VF_E_INVALID when kh rows of a frame do not fit it. */
+int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                        const int *widths, const int *heights, int n, int channels,
+                        const int16_t *weights, int kw, int kh, int shift, int border);
+
+/* vf_jpeg_invert with the convolution in place of the inversion: decode -> cv2.filter2D ->
+ * encode on the GPU; channel c of the kernel's view is channel c of the decoded BGR frame. */
+int vf_jpeg_conv(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                 const int16_t *weights, int kw, int kh, int shift, int border, int quality,
+                 int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the convolution (weights copied).  The ticket is an invert
+ * ticket: collect with vf_jpeg_invert_query / _wait / _fetch / _scatter. */
+int vf_jpeg_conv_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                        const int16_t *weights, int kw, int kh, int shift, int border, int quality,
+                        int subsamp, int flags, uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the convolution between the decode and the encode. */
+int vf_jpeg_bench_conv(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                       const int16_t *weights, int kw, int kh, int shift, int border, int quality,
+                       int subsamp, int flags, int iters, float *ms, float *stage_ms);
+
 #ifdef __cplusplus
 }
 #endif
