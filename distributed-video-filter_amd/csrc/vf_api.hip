@@ -77,12 +77,13 @@ struct vf_ctx {
   std::atomic<uint64_t> jpeg_max_pixels{vf::jpeg::kDefaultMaxPixels};
   // vf_bench_device_ring's region events, created once (not inside a caller's timed region)
   hipEvent_t bench_ev[2] = {nullptr, nullptr};
-  // vf_lut_frames_host: a stream and one input and one output device buffer of lut_cap (+ slack)
-  // bytes, created by the first call; lut_cap is the engine's slot size
-  std::mutex lut_mu;
-  size_t lut_cap = 0;
-  hipStream_t lut_stream = nullptr;
-  uint8_t *lut_din = nullptr, *lut_dout = nullptr;
+  // the raw host path's staging, shared by vf_lut_frames_host and vf_conv_frames_host: a stream and
+  // one input and one output device buffer of raw_cap (+ slack) bytes, created by the first call of
+  // either; raw_cap is the engine's slot size
+  std::mutex raw_mu;
+  size_t raw_cap = 0;
+  hipStream_t raw_stream = nullptr;
+  uint8_t *raw_din = nullptr, *raw_dout = nullptr;
 };
 
 namespace {
@@ -250,19 +251,19 @@ VF_EXPORT int vf_create(int device, size_t max_frame_bytes, int max_batch, vf_ct
     delete ctx;
     return st;
   }
-  ctx->lut_cap = slot;
+  ctx->raw_cap = slot;
   *out = ctx;
   return VF_OK;
 }
 
 VF_EXPORT int vf_destroy(vf_ctx *ctx) {
   if (!ctx) return VF_OK;
-  if (ctx->lut_stream) {
+  if (ctx->raw_stream) {
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->lut_stream);
-    (void)hipFree(ctx->lut_din);
-    (void)hipFree(ctx->lut_dout);
-    (void)hipStreamDestroy(ctx->lut_stream);
+    (void)hipStreamSynchronize(ctx->raw_stream);
+    (void)hipFree(ctx->raw_din);
+    (void)hipFree(ctx->raw_dout);
+    (void)hipStreamDestroy(ctx->raw_stream);
   }
   for (vf::jpeg::Codec *c : ctx->jpeg_all) delete c;  // each synchronises its stream first
   delete ctx->engine;  // finishes queued jobs first
@@ -379,9 +380,9 @@ int check_table(vf_ctx *ctx, const char *fn, const uint8_t *table, int channels)
   return VF_OK;
 }
 
-// vf_lut_frames_host's stream and device buffers (ctx->lut_mu held).
-int lut_staging(vf_ctx *ctx, size_t alloc) {
-  if (ctx->lut_stream) return VF_OK;
+// The raw host path's stream and device buffers (ctx->raw_mu held); fn: the entry point that asks.
+int raw_staging(vf_ctx *ctx, const char *fn, size_t alloc) {
+  if (ctx->raw_stream) return VF_OK;
   hipStream_t st = nullptr;
   VF_HIP(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   void *din = nullptr, *dout = nullptr;
@@ -390,11 +391,11 @@ int lut_staging(vf_ctx *ctx, size_t alloc) {
   if (e != hipSuccess) {
     (void)hipFree(din);
     (void)hipStreamDestroy(st);
-    return set_err(ctx, VF_E_NOMEM, (int)e, "vf_lut_frames_host: hipMalloc(%zu) failed: %s", alloc, hipGetErrorString(e));
+    return set_err(ctx, VF_E_NOMEM, (int)e, "%s: hipMalloc(%zu) failed: %s", fn, alloc, hipGetErrorString(e));
   }
-  ctx->lut_din = static_cast<uint8_t *>(din);
-  ctx->lut_dout = static_cast<uint8_t *>(dout);
-  ctx->lut_stream = st;
+  ctx->raw_din = static_cast<uint8_t *>(din);
+  ctx->raw_dout = static_cast<uint8_t *>(dout);
+  ctx->raw_stream = st;
   return VF_OK;
 }
 
@@ -432,14 +433,14 @@ VF_EXPORT int vf_lut_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_
     frames.push_back(vf::lut::Frame{sg.src, sg.dst, sg.len});
   }
   if (frames.empty()) return VF_OK;
-  std::lock_guard<std::mutex> lk(ctx->lut_mu);
+  std::lock_guard<std::mutex> lk(ctx->raw_mu);
   VF_HIP(ctx, hipSetDevice(ctx->device));
   // a piece sits in both device buffers at its caller pointers' offsets mod 16 past a 16-B
   // boundary, so the copies and the kernel see the caller's alignment: up to 15 bytes of slack
-  const size_t cap = ctx->lut_cap, alloc = ((cap + 15 + 15) & ~(size_t)15);
-  if ((rc = lut_staging(ctx, alloc)) != VF_OK) return rc;
+  const size_t cap = ctx->raw_cap, alloc = ((cap + 15 + 15) & ~(size_t)15);
+  if ((rc = raw_staging(ctx, "vf_lut_frames_host", alloc)) != VF_OK) return rc;
   const std::vector<vf::lut::Launch> ls = vf::lut::split(frames, cap, channels);
-  hipStream_t st = ctx->lut_stream;
+  hipStream_t st = ctx->raw_stream;
   std::vector<size_t> at(ls.size());
   for (size_t i = 0; i < ls.size();) {
     // one fill of the buffers: upload and filter the pieces that fit, download them, wait
@@ -447,15 +448,15 @@ VF_EXPORT int vf_lut_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_
     for (; j < ls.size(); ++j) {
       const size_t room = (ls[j].len + 15 + 15) & ~(size_t)15;
       if (cur + room > alloc) break;
-      const uint8_t *din = ctx->lut_din + cur + ((uintptr_t)ls[j].src & 15);
-      uint8_t *dout = ctx->lut_dout + cur + ((uintptr_t)ls[j].dst & 15);
+      const uint8_t *din = ctx->raw_din + cur + ((uintptr_t)ls[j].src & 15);
+      uint8_t *dout = ctx->raw_dout + cur + ((uintptr_t)ls[j].dst & 15);
       at[j] = cur;
       cur += room;
       VF_HIP(ctx, hipMemcpyAsync(const_cast<uint8_t *>(din), ls[j].src, ls[j].len, hipMemcpyHostToDevice, st));
       VF_HIP(ctx, vf::launch_lut(din, dout, ls[j].len, table, channels, ls[j].phase, ctx->cfg, st));
     }
     for (size_t k = i; k < j; ++k)
-      VF_HIP(ctx, hipMemcpyAsync(ls[k].dst, ctx->lut_dout + at[k] + ((uintptr_t)ls[k].dst & 15), ls[k].len,
+      VF_HIP(ctx, hipMemcpyAsync(ls[k].dst, ctx->raw_dout + at[k] + ((uintptr_t)ls[k].dst & 15), ls[k].len,
                                  hipMemcpyDeviceToHost, st));
     VF_HIP(ctx, hipStreamSynchronize(st));
     i = j;
@@ -531,7 +532,7 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
   };
   std::vector<Piece> pieces;
   std::vector<std::vector<uint8_t>> saved;
-  const size_t cap = ctx->lut_cap;
+  const size_t cap = ctx->raw_cap;
   const int ry = kh / 2;
   for (int i = 0; i < n; ++i) {
     if (widths[i] == 0 && heights[i] == 0) continue;  // the empty frame
@@ -554,11 +555,11 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
     }
   }
   if (pieces.empty()) return VF_OK;
-  std::lock_guard<std::mutex> lk(ctx->lut_mu);
+  std::lock_guard<std::mutex> lk(ctx->raw_mu);
   VF_HIP(ctx, hipSetDevice(ctx->device));
   const size_t alloc = ((cap + 15 + 15) & ~(size_t)15);
-  if ((rc = lut_staging(ctx, alloc)) != VF_OK) return rc;
-  hipStream_t st = ctx->lut_stream;
+  if ((rc = raw_staging(ctx, fn, alloc)) != VF_OK) return rc;
+  hipStream_t st = ctx->raw_stream;
   const int form = vf::conv_form_env();
   std::vector<size_t> at(pieces.size());
   for (size_t i = 0; i < pieces.size();) {
@@ -569,7 +570,7 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
       const size_t row = (size_t)widths[p.frame] * (size_t)channels;
       const size_t in_bytes = (size_t)(p.b.s1 - p.b.s0) * row, out_bytes = (size_t)(p.b.y1 - p.b.y0) * row;
       if (cin + in_bytes > alloc || cout + out_bytes > alloc) break;
-      uint8_t *din = ctx->lut_din + cin, *dout = ctx->lut_dout + cout;
+      uint8_t *din = ctx->raw_din + cin, *dout = ctx->raw_dout + cout;
       const uint8_t *src = srcs[p.frame];
       size_t head = 0;
       if (p.halo) {
@@ -586,7 +587,7 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
     for (size_t k = i; k < j; ++k) {
       const Piece &p = pieces[k];
       const size_t row = (size_t)widths[p.frame] * (size_t)channels;
-      VF_HIP(ctx, hipMemcpyAsync(dsts[p.frame] + (size_t)p.b.y0 * row, ctx->lut_dout + at[k],
+      VF_HIP(ctx, hipMemcpyAsync(dsts[p.frame] + (size_t)p.b.y0 * row, ctx->raw_dout + at[k],
                                  (size_t)(p.b.y1 - p.b.y0) * row, hipMemcpyDeviceToHost, st));
     }
     VF_HIP(ctx, hipStreamSynchronize(st));
@@ -924,10 +925,11 @@ VF_EXPORT int vf_jpeg_decode(vf_ctx *ctx, const uint8_t *const *jpegs, const siz
 
 namespace {
 
-// decode -> filter -> encode for vf_jpeg_invert (lut == nullptr: bitwise_not) and vf_jpeg_lut
+using vf::jpeg::Filter;
+
+// decode -> filter -> encode, for every vf_jpeg_{invert,lut,conv}
 int jpeg_filter(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
-                int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes, const uint8_t *lut,
-                int channels, const vf::jpeg::ConvSpec *conv = nullptr) {
+                int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes, const Filter &filt) {
   if (n < 0 || (n > 0 && (!jpegs || !jpeg_sizes || !outs || !caps || !sizes)))
     return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
   if (n > 65535) return set_err(ctx, VF_E_INVALID, 0, "%s: at most 65535 frames per call", fn);
@@ -936,13 +938,12 @@ int jpeg_filter(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const 
   int rc = jpeg_codec(ctx, lease, &c);
   if (rc) return rc;
   std::string err;
-  rc = c->invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, &err, lut, channels, conv);
+  rc = c->invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filt, &err);
   return jpeg_status(ctx, rc, std::string(fn) + ": " + err);
 }
 
 int jpeg_filter_submit(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
-                       int quality, int subsamp, int flags, uint64_t *ticket, const uint8_t *lut, int channels,
-                       const vf::jpeg::ConvSpec *conv = nullptr) {
+                       int quality, int subsamp, int flags, uint64_t *ticket, const Filter &filt) {
   if (!ticket || n <= 0 || n > 65535 || !jpegs || !jpeg_sizes)
     return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
   *ticket = 0;
@@ -950,7 +951,7 @@ int jpeg_filter_submit(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs,
   if (!c)
     return set_err(ctx, VF_E_INVALID, 0, "%s: %zu batches already in flight; fetch one first", fn, kMaxJpegJobs);
   std::string err;
-  const int rc = c->submit_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, &err, lut, channels, conv);
+  const int rc = c->submit_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, filt, &err);
   if (rc != VF_OK) {
     c->quiesce();  // a submit that failed after queueing work must not hand the codec on mid-flight
     give_back(ctx, c);
@@ -963,8 +964,7 @@ int jpeg_filter_submit(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs,
 }
 
 int jpeg_filter_bench(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
-                      int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms, const uint8_t *lut,
-                      int channels, const vf::jpeg::ConvSpec *conv = nullptr) {
+                      int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms, const Filter &filt) {
   if (n <= 0 || n > 65535 || !jpegs || !jpeg_sizes || !ms || iters <= 0)
     return set_err(ctx, VF_E_INVALID, 0, "%s: bad arguments", fn);
   CodecLease lease(ctx);
@@ -972,21 +972,28 @@ int jpeg_filter_bench(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, 
   int rc = jpeg_codec(ctx, lease, &c);
   if (rc) return rc;
   std::string err;
-  rc = c->bench_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms, &err, lut, channels, conv);
+  rc = c->bench_invert(jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, filt, ms, stage_ms, &err);
   return jpeg_status(ctx, rc, std::string(fn) + ": " + err);
 }
 
-// the checked kernel of a vf_jpeg_conv* call as the codec takes it
-int conv_spec(vf_ctx *ctx, const char *fn, const int16_t *weights, int kw, int kh, int shift, int border,
-              vf::jpeg::ConvSpec *out) {
+// The two builders of a batch's filter from an entry point's arguments, checked first (fn: its
+// name, for the message).  The inversion is Filter{}.
+int table_filter(vf_ctx *ctx, const char *fn, const uint8_t *table, int channels, Filter *out) {
+  const int rc = check_table(ctx, fn, table, channels);
+  if (rc != VF_OK) return rc;
+  out->kind = Filter::kTable;
+  uint8_t *t = reinterpret_cast<uint8_t *>(out->lut.w);  // a one-channel table serves all three
+  for (int c = 0; c < 3; ++c) std::memcpy(t + 256 * c, table + (channels == 3 ? 256 * c : 0), 256);
+  return VF_OK;
+}
+
+int conv_filter(vf_ctx *ctx, const char *fn, const int16_t *weights, int kw, int kh, int shift, int border,
+                Filter *out) {
   const int rc = check_kernel(ctx, fn, weights, kw, kh, shift, border);
   if (rc != VF_OK) return rc;
-  std::memset(out, 0, sizeof *out);
-  std::memcpy(out->w, weights, sizeof(int16_t) * (size_t)(kw * kh));
-  out->kw = kw;
-  out->kh = kh;
-  out->shift = shift;
-  out->border = border;
+  out->kind = Filter::kConv;
+  out->conv = vf::jpeg::ConvSpec{{}, kw, kh, shift, border};
+  std::memcpy(out->conv.w, weights, sizeof(int16_t) * (size_t)(kw * kh));
   return VF_OK;
 }
 
@@ -995,34 +1002,32 @@ int conv_spec(vf_ctx *ctx, const char *fn, const int16_t *weights, int kw, int k
 VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
                              int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes) {
   VF_CHECK_CTX(ctx);
-  return jpeg_filter(ctx, "vf_jpeg_invert", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, nullptr, 0);
+  return jpeg_filter(ctx, "vf_jpeg_invert", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, Filter{});
 }
 
 VF_EXPORT int vf_jpeg_invert_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                                     int quality, int subsamp, int flags, uint64_t *ticket) {
   VF_CHECK_CTX(ctx);
   return jpeg_filter_submit(ctx, "vf_jpeg_invert_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket,
-                            nullptr, 0);
+                            Filter{});
 }
 
 VF_EXPORT int vf_jpeg_lut(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                           const uint8_t *table, int channels, int quality, int subsamp, int flags,
                           uint8_t *const *outs, const size_t *caps, size_t *sizes) {
   VF_CHECK_CTX(ctx);
-  const int rc = check_table(ctx, "vf_jpeg_lut", table, channels);
-  if (rc != VF_OK) return rc;
-  return jpeg_filter(ctx, "vf_jpeg_lut", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, table,
-                     channels);
+  Filter filter;
+  if (const int rc = table_filter(ctx, "vf_jpeg_lut", table, channels, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_lut", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
 }
 
 VF_EXPORT int vf_jpeg_lut_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                                  const uint8_t *table, int channels, int quality, int subsamp, int flags,
                                  uint64_t *ticket) {
   VF_CHECK_CTX(ctx);
-  const int rc = check_table(ctx, "vf_jpeg_lut_submit", table, channels);
-  if (rc != VF_OK) return rc;
-  return jpeg_filter_submit(ctx, "vf_jpeg_lut_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, table,
-                            channels);
+  Filter filter;
+  if (const int rc = table_filter(ctx, "vf_jpeg_lut_submit", table, channels, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_lut_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
 }
 
 VF_EXPORT int vf_jpeg_invert_query(vf_ctx *ctx, uint64_t ticket, int *done) {
@@ -1077,48 +1082,43 @@ VF_EXPORT int vf_jpeg_bench_invert(vf_ctx *ctx, const uint8_t *const *jpegs, con
                                    int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms) {
   VF_CHECK_CTX(ctx);
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_invert", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
-                           stage_ms, nullptr, 0);
+                           stage_ms, Filter{});
 }
 
 VF_EXPORT int vf_jpeg_bench_lut(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                                 const uint8_t *table, int channels, int quality, int subsamp, int flags, int iters,
                                 float *ms, float *stage_ms) {
   VF_CHECK_CTX(ctx);
-  const int rc = check_table(ctx, "vf_jpeg_bench_lut", table, channels);
-  if (rc != VF_OK) return rc;
+  Filter filter;
+  if (const int rc = table_filter(ctx, "vf_jpeg_bench_lut", table, channels, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_lut", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
-                           table, channels);
+                           filter);
 }
 
 VF_EXPORT int vf_jpeg_conv(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                            const int16_t *weights, int kw, int kh, int shift, int border, int quality, int subsamp,
                            int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes) {
   VF_CHECK_CTX(ctx);
-  vf::jpeg::ConvSpec spec;
-  const int rc = conv_spec(ctx, "vf_jpeg_conv", weights, kw, kh, shift, border, &spec);
-  if (rc != VF_OK) return rc;
-  return jpeg_filter(ctx, "vf_jpeg_conv", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, nullptr, 0,
-                     &spec);
+  Filter filter;
+  if (const int rc = conv_filter(ctx, "vf_jpeg_conv", weights, kw, kh, shift, border, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_conv", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
 }
 
 VF_EXPORT int vf_jpeg_conv_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                                   const int16_t *weights, int kw, int kh, int shift, int border, int quality,
                                   int subsamp, int flags, uint64_t *ticket) {
   VF_CHECK_CTX(ctx);
-  vf::jpeg::ConvSpec spec;
-  const int rc = conv_spec(ctx, "vf_jpeg_conv_submit", weights, kw, kh, shift, border, &spec);
-  if (rc != VF_OK) return rc;
-  return jpeg_filter_submit(ctx, "vf_jpeg_conv_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, nullptr,
-                            0, &spec);
+  Filter filter;
+  if (const int rc = conv_filter(ctx, "vf_jpeg_conv_submit", weights, kw, kh, shift, border, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_conv_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
 }
 
 VF_EXPORT int vf_jpeg_bench_conv(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                                  const int16_t *weights, int kw, int kh, int shift, int border, int quality,
                                  int subsamp, int flags, int iters, float *ms, float *stage_ms) {
   VF_CHECK_CTX(ctx);
-  vf::jpeg::ConvSpec spec;
-  const int rc = conv_spec(ctx, "vf_jpeg_bench_conv", weights, kw, kh, shift, border, &spec);
-  if (rc != VF_OK) return rc;
+  Filter filter;
+  if (const int rc = conv_filter(ctx, "vf_jpeg_bench_conv", weights, kw, kh, shift, border, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_conv", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
-                           stage_ms, nullptr, 0, &spec);
+                           stage_ms, filter);
 }

@@ -97,6 +97,17 @@ struct ConvSpec {
   int kw, kh, shift, border;
 };
 
+// The filter of one batch of the invert path, as one value (vf_api.hip builds it from an entry point's
+// checked arguments); default-constructed, the inversion (cv2.bitwise_not).  The codec copies it, so
+// a batch resynchronised at wait_invert is filtered again by the same table or kernel.
+struct Filter {
+  enum Kind { kNone, kInvert, kTable, kConv } kind = kInvert;  // kNone: the plain decode, pixels stay as decoded
+  LutTable lut = {};   // kTable: cv2.LUT on the decoded BGR pixels; a one-channel table is stored three times
+  ConvSpec conv = {};  // kConv: cv2.filter2D on them
+  bool in_colour() const { return kind == kInvert || kind == kTable; }  // the colour stage filters
+  bool between() const { return kind == kConv; }  // a convolution runs between decode (d_pix_) and encode (d_pix2_)
+};
+
 int header_info(const uint8_t *jpeg, size_t size, int *w, int *h, int *subsamp, int *colorspace, std::string *err);
 size_t buffer_size(int w, int h, int subsamp);
 
@@ -112,20 +123,14 @@ class Codec {
              int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes, std::string *err);
   int decode(const uint8_t *const *jpegs, const size_t *sizes, int n, int pixel_format, int flags,
              uint8_t *const *outs, const size_t *caps, std::string *err);
-  // lut (here and in submit_invert, bench_invert): `channels` (1 or 3) planar 256-byte tables
-  // applied to the decoded BGR pixels in place of the inversion (cv2.LUT); read during the call
   int invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
-             uint8_t *const *outs, const size_t *caps, size_t *out_sizes, std::string *err,
-             const uint8_t *lut = nullptr, int channels = 0, const ConvSpec *conv = nullptr);
-  // conv (here and in submit_invert, bench_invert; copied): cv2.filter2D on the decoded BGR pixels in
-  // place of the inversion, through the unfused pixel round trip: decode into d_pix_, the
-  // convolution kernel per frame into d_pix2_, which the encoder reads
+             uint8_t *const *outs, const size_t *caps, size_t *out_sizes, const Filter &filter, std::string *err);
   // invert() in three steps, so one host thread can keep batches of two codecs in flight:
   // submit_invert returns once everything is queued (inputs staged: the caller's buffers may go);
   // done_invert never blocks; wait_invert blocks and gives the packed output size; fetch_invert
   // copies the packed outputs (frame f at offs[f], sizes[f] bytes; out may be NULL).
   int submit_invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
-                    std::string *err, const uint8_t *lut = nullptr, int channels = 0, const ConvSpec *conv = nullptr);
+                    const Filter &filter, std::string *err);
   bool done_invert();
   int wait_invert(size_t *total, std::string *err);
   int fetch_invert(uint8_t *out, size_t cap, size_t *sizes, size_t *offs, std::string *err);
@@ -142,21 +147,19 @@ class Codec {
   // the device part of invert() `iters` times on resident inputs; mean wall ms per iteration,
   // stage_ms[0..6] = unstuff, sync, write, dc+idct, colour, fdct+huffman, stuffing; [7] = passes
   int bench_invert(const uint8_t *const *jpegs, const size_t *sizes, int n, int quality, int subsamp, int flags,
-                   int iters, float *ms, float *stage_ms, std::string *err, const uint8_t *lut = nullptr,
-                   int channels = 0, const ConvSpec *conv = nullptr);
+                   int iters, const Filter &filter, float *ms, float *stage_ms, std::string *err);
 
  private:
   int init(std::string *err);
   int prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int n, int flags, const JpegSwitches &sw,
-                     bool invert, std::string *err);  // parse, layout, uploads; resolves plan_
-  int run_decode(int bgr, bool invert, std::string *err);
-  int run_decode_post(int bgr, bool invert, std::string *err);  // write, DC, IDCT, colour
-  int set_filter(const uint8_t *lut, int channels, std::string *err);
+                     std::string *err);  // parse, layout, uploads; resolves plan_
+  int run_decode(int bgr, std::string *err);
+  int run_decode_post(int bgr, std::string *err);  // write, DC, IDCT, colour
   hipError_t span_pass(int p);
   int finish_sync(std::string *err);  // host-looped span passes after the queued ones
   int check_decode(std::string *err);
   template <class Tail>  // the one resync loop: check, finish_sync, run_decode_post, tail, check again
-  int settle_decode(int bgr, bool invert, Tail &&tail, std::string *err);
+  int settle_decode(int bgr, Tail &&tail, std::string *err);
   int prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs, int n, int quality, int subsamp,
                      bool fastdct, std::string *err);
   // pix: the BGR / RGB pixels the encoder reads when the plan is not fused (d_pix_ or d_pix2_)
@@ -204,10 +207,7 @@ class Codec {
   uint32_t emax_blocks_ = 0, emax_tiles_ = 0;
   uint64_t eblocks_ = 0, ebits_bytes_ = 0;
   DevBuf d_eplanes_;  // the invert path's encoder sample planes (plan_.fuse)
-  bool has_lut_ = false;  // the invert path's filter is lut_ (else the inversion)
-  LutTable lut_ = {};
-  bool has_conv_ = false;  // the invert path's filter is conv_, applied between decode and encode
-  ConvSpec conv_ = {};
+  Filter filter_;  // the batch's filter, set by the entry call before prepare_decode; the stages read it
   DevBuf d_pix2_;  // the convolution's output: the batch's frames at their d_pix_ offsets
   int dcm_ = -1;  // k_color layout shared by the batch's frames (1..3, 0 general), -1 mixed
   DevBuf d_efr_, d_etab_, d_hdr_, d_esegs_, d_etsum_, d_etotals_, d_dcq_, d_acbits_, d_acscr_, d_bits_, d_pre_, d_bitoff_, d_stream_, d_ffcnt_,

@@ -271,7 +271,7 @@ int Codec::init(std::string *err) {
 // Host parse of every frame + batch layout + upload of inputs and descriptors.
 // Ends with the batch's plan (vf_jpeg_plan.h), resolved from the entry call's switches.
 int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int n, int flags, const JpegSwitches &sw,
-                          bool invert, std::string *err) {
+                          std::string *err) {
   if (n <= 0) {
     *err = "empty batch";
     return kInvalid;
@@ -549,13 +549,13 @@ int Codec::prepare_decode(const uint8_t *const *jpegs, const size_t *sizes, int 
     prep_ms_[2] = ms(tp2, clk::now());
   }
   traits.max_sub = dmax_sub_;
-  plan_ = resolve(sw, traits, invert);
+  plan_ = resolve(sw, traits, filter_.in_colour());
   plan_.enc_fast = (flags & kFlagFastDct) != 0;
   return kOk;
 }
 
 // Device part of the decode: unstuff -> sync passes -> write -> DC -> IDCT -> colour.
-int Codec::run_decode(int bgr, bool invert, std::string *err) {
+int Codec::run_decode(int bgr, std::string *err) {
   const DecFrame *fr = d_dfr_.as<DecFrame>();
   const DecSeg *sg = d_dsg_.as<DecSeg>();
   const ScanSeg *segs = d_segs_.as<ScanSeg>();
@@ -648,7 +648,7 @@ int Codec::run_decode(int bgr, bool invert, std::string *err) {
                  (dmax_sub_ + 255) / 256 * (uint32_t)ns);
   }
   CK(stage_event(2));
-  return run_decode_post(bgr, invert, err);
+  return run_decode_post(bgr, err);
 }
 
 // Span pass p of the plan's width and table layout, on the batch's unstuffed segments.
@@ -679,7 +679,7 @@ int Codec::finish_sync(std::string *err) {
 }
 
 // Decode stages after the sync: block offsets, write pass, DC prediction, IDCT, colour.
-int Codec::run_decode_post(int bgr, bool invert, std::string *err) {
+int Codec::run_decode_post(int bgr, std::string *err) {
   const DecFrame *fr = d_dfr_.as<DecFrame>();
   const DecSeg *sg = d_dsg_.as<DecSeg>();
   const ScanSeg *segs = d_segs_.as<ScanSeg>();
@@ -687,7 +687,8 @@ int Codec::run_decode_post(int bgr, bool invert, std::string *err) {
   const uint32_t *us_len = d_totals_.as<uint32_t>();
   const DecodePlan &pl = plan_;
   const int last = sync_slot_;
-  const LutTable *const lut = invert && has_lut_ ? &lut_ : nullptr;  // the batch's filter table (set_filter)
+  const bool invert = filter_.in_colour();
+  const LutTable *const lut = filter_.kind == Filter::kTable ? &filter_.lut : nullptr;  // in place of the inversion
   // 3. block offsets of the subsequences, then the write pass
   // the segments' decoded block counts go straight to the page-locked h_dtot_ (check_decode)
   uint32_t *blocks_total = static_cast<uint32_t *>(dtot_dev_);
@@ -876,12 +877,13 @@ int Codec::prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs
 // d_pix2_ at the same offset and the encoder reads that.  settle_decode's tails call this, so a
 // batch resynchronised at wait_invert is filtered again from freshly decoded pixels: once.
 int Codec::run_filter_encode(bool fastdct, std::string *err) {
-  if (!has_conv_) return run_encode(1, fastdct, d_pix_.as<uint8_t>(), err);
+  if (!filter_.between()) return run_encode(1, fastdct, d_pix_.as<uint8_t>(), err);
   CK(d_pix2_.ensure(dpix_bytes_));
+  const ConvSpec &k = filter_.conv;
   for (int f = 0; f < dn_; ++f) {
     const DecFrame &F = dfr_[(size_t)f];
     CK(launch_conv(d_pix_.as<uint8_t>() + F.out_off, d_pix2_.as<uint8_t>() + F.out_off, F.g.w, 3, F.g.h, 0, F.g.h, 0,
-                   F.g.h, conv_.w, conv_.kw, conv_.kh, conv_.shift, conv_.border, 0, s_));
+                   F.g.h, k.w, k.kw, k.kh, k.shift, k.border, 0, s_));
   }
   return run_encode(1, fastdct, d_pix2_.as<uint8_t>(), err);
 }
@@ -965,10 +967,10 @@ int Codec::finish_fetch(std::string *err) {
 // the sync again, then `tail` -- whatever the caller queues behind the decode, ending with its
 // wait -- and the checks again.
 template <class Tail>
-int Codec::settle_decode(int bgr, bool invert, Tail &&tail, std::string *err) {
+int Codec::settle_decode(int bgr, Tail &&tail, std::string *err) {
   int rc = check_decode(err);
   while (rc == kResync) {
-    if ((rc = finish_sync(err)) || (rc = run_decode_post(bgr, invert, err)) || (rc = tail())) return rc;
+    if ((rc = finish_sync(err)) || (rc = run_decode_post(bgr, err)) || (rc = tail())) return rc;
     rc = check_decode(err);
   }
   return rc;
@@ -998,7 +1000,7 @@ int Codec::encode(const uint8_t *const *imgs, const int *ws, const int *hs, int 
   const bool fast = (flags & kFlagFastDct) != 0;
   if ((rc = prepare_encode(ws, hs, offs.data(), n, quality, subsamp, fast, err))) return rc;
   plan_ = DecodePlan();  // no decode, no switches: run_encode reads pixels (plan_.fuse off)
-  has_conv_ = false;
+  filter_ = Filter{};
   CK(h_stage_.ensure(pix));
   CK(d_pix_.ensure(pix));
   pool_.run(n, [&](int f) {
@@ -1040,7 +1042,8 @@ int Codec::decode(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
     *err = "pixel_format must be TJPF_RGB (0) or TJPF_BGR (1)";
     return kInvalid;
   }
-  if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), false, err))) return rc;
+  filter_.kind = Filter::kNone;
+  if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), err))) return rc;
   for (int f = 0; f < n; ++f) {
     const size_t need = (size_t)dfr_[(size_t)f].g.w * dfr_[(size_t)f].g.h * 3;
     if (!outs[f] || caps[f] < need) {
@@ -1048,14 +1051,14 @@ int Codec::decode(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
       return kInvalid;
     }
   }
-  if ((rc = run_decode(pixel_format, false, err))) return rc;
+  if ((rc = run_decode(pixel_format, err))) return rc;
   auto fetch_pixels = [&]() -> int {
     CK(h_out_.ensure(dpix_bytes_));
     CK(hipMemcpyAsync(h_out_.p, d_pix_.p, dpix_bytes_, hipMemcpyDeviceToHost, s_));
     CK(hipStreamSynchronize(s_));
     return kOk;
   };
-  if ((rc = fetch_pixels()) || (rc = settle_decode(pixel_format, false, fetch_pixels, err))) return rc;
+  if ((rc = fetch_pixels()) || (rc = settle_decode(pixel_format, fetch_pixels, err))) return rc;
   pool_.run(n, [&](int f) {
     std::memcpy(outs[f], h_out_.as<uint8_t>() + dfr_[(size_t)f].out_off,
                 (size_t)dfr_[(size_t)f].g.w * dfr_[(size_t)f].g.h * 3);
@@ -1067,31 +1070,12 @@ int Codec::decode(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
 // submit_invert (parse, stage, queue every upload, kernel and download; returns without
 // waiting for the GPU), wait_invert (the done event, the decode checks, the packed layout),
 // fetch_invert (copy-out).  invert() is the three in a row.
-// The filter of the invert path's next batch: cv2.LUT with `channels` (1 or 3) planar 256-byte
-// tables for the BGR pixel's channels, or, with no table, cv2.bitwise_not.  The codec keeps a
-// copy, so a batch resynchronised at wait_invert runs its colour pass with the same table.
-int Codec::set_filter(const uint8_t *lut, int channels, std::string *err) {
-  has_lut_ = lut != nullptr;
-  if (!lut) return kOk;
-  if (channels != 1 && channels != 3) {
-    has_lut_ = false;
-    *err = "table channels must be 1 or 3";
-    return kInvalid;
-  }
-  uint8_t *t = reinterpret_cast<uint8_t *>(lut_.w);
-  for (int c = 0; c < 3; ++c) std::memcpy(t + 256 * c, lut + (channels == 3 ? 256 * c : 0), 256);
-  return kOk;
-}
-
 int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp,
-                         int flags, std::string *err, const uint8_t *lut, int channels, const ConvSpec *conv) {
+                         int flags, const Filter &filter, std::string *err) {
   int rc = init(err);
   if (rc) return rc;
   waited_ = false;
-  if ((rc = set_filter(lut, channels, err))) return rc;
-  has_conv_ = conv != nullptr;
-  if (conv) conv_ = *conv;
-  const bool inv = !has_conv_;  // the colour stage filters (inversion or table); else plain pixels for the convolution
+  filter_ = filter;
   if (n <= 0) {
     *err = "empty batch";
     return kInvalid;
@@ -1099,7 +1083,7 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
   const JpegSwitches sw = JpegSwitches::read();
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
-  if ((rc = prepare_decode(jpegs, jsizes, n, flags, sw, inv, err))) return rc;
+  if ((rc = prepare_decode(jpegs, jsizes, n, flags, sw, err))) return rc;
   const auto t1 = clk::now();
   std::vector<int> ws((size_t)n), hs((size_t)n);
   std::vector<uint64_t> offs((size_t)n);
@@ -1128,7 +1112,7 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
       if (gate_->last) CK(hipStreamWaitEvent(s_, gate_->last, 0));
     }
     // decode (BGR, inverted: cv2.bitwise_not, inverter.py:41) straight into the encoder's input
-    if ((rc = run_decode(1, inv, err))) return rc;
+    if ((rc = run_decode(1, err))) return rc;
     if ((rc = run_filter_encode(plan_.enc_fast, err))) return rc;
     if (gate_) {
       CK(hipEventRecord(ev_[9], s_));
@@ -1166,7 +1150,7 @@ int Codec::wait_invert(size_t *total, std::string *err) {
   CK(hipEventSynchronize(done_));
   // everything from here on follows the plan submit_invert left: this may run on another thread,
   // under another environment
-  int rc = settle_decode(1, !has_conv_, [&]() -> int {
+  int rc = settle_decode(1, [&]() -> int {
     int r = run_filter_encode(plan_.enc_fast, err);
     if (!r) r = queue_fetch(guess_, err);
     if (r) return r;
@@ -1224,10 +1208,9 @@ int Codec::fetch_invert(uint8_t *out, size_t cap, size_t *sizes, size_t *offs, s
 }
 
 int Codec::invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp, int flags,
-                  uint8_t *const *outs, const size_t *caps, size_t *sizes, std::string *err, const uint8_t *lut,
-                  int channels, const ConvSpec *conv) {
+                  uint8_t *const *outs, const size_t *caps, size_t *sizes, const Filter &filter, std::string *err) {
   if (n <= 0) return init(err);
-  int rc = submit_invert(jpegs, jsizes, n, quality, subsamp, flags, err, lut, channels, conv);
+  int rc = submit_invert(jpegs, jsizes, n, quality, subsamp, flags, filter, err);
   size_t total = 0;
   if (!rc) rc = wait_invert(&total, err);
   if (!rc) rc = copy_out(outs, caps, sizes, err);
@@ -1235,19 +1218,15 @@ int Codec::invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int 
 }
 
 int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n, int quality, int subsamp,
-                        int flags, int iters, float *ms, float *stage_ms, std::string *err, const uint8_t *lut,
-                        int channels, const ConvSpec *conv) {
+                        int flags, int iters, const Filter &filter, float *ms, float *stage_ms, std::string *err) {
   int rc = init(err);
   if (rc) return rc;
   if (n <= 0 || iters <= 0) {
     *err = "bench_invert: empty batch or iters <= 0";
     return kInvalid;
   }
-  if ((rc = set_filter(lut, channels, err))) return rc;
-  has_conv_ = conv != nullptr;
-  if (conv) conv_ = *conv;
-  const bool inv = !has_conv_;
-  if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), inv, err))) return rc;
+  filter_ = filter;
+  if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), err))) return rc;
   std::vector<int> ws((size_t)n), hs((size_t)n);
   std::vector<uint64_t> offs((size_t)n);
   for (int f = 0; f < n; ++f) {
@@ -1268,7 +1247,7 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
     for (int it = 0; it < iters; ++it) {
       CK(hipStreamSynchronize(s_));
       const auto t0 = std::chrono::steady_clock::now();
-      if ((rc = run_decode(1, inv, err)) || (rc = run_filter_encode(fast, err))) {
+      if ((rc = run_decode(1, err)) || (rc = run_filter_encode(fast, err))) {
         stage_events_ = false;
         return rc;
       }
@@ -1288,7 +1267,7 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
   }
   stage_events_ = false;
   CK(hipStreamSynchronize(s_));
-  rc = settle_decode(1, inv, [&]() -> int {
+  rc = settle_decode(1, [&]() -> int {
     const int r = run_filter_encode(fast, err);
     if (r) return r;
     CK(hipStreamSynchronize(s_));

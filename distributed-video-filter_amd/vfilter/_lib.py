@@ -292,6 +292,7 @@ class Context:
             raise VFilterError(self._lib.vf_last_error(None).decode(), st, self._lib.vf_last_hip_error(None))
         self.device = int(device)
         self._arena = _PinnedArena(self)
+        self._jpeg_n = {}  # ticket -> frame count of every submitted JPEG batch not yet collected
 
     @property
     def _ctx(self):
@@ -616,6 +617,61 @@ class Context:
         self._check(self._lib.vf_jpeg_decode(self._ctx, ja, js, n, pixel_format, flags, oa, ca))
         return outs
 
+    # The three JPEG filters differ in one C function each and in the arguments that stand between the
+    # batch and the quality, ``extra`` below: none (invert), ``table, channels`` (lut), ``weights, kw,
+    # kh, shift, border`` (conv).  The pointers keep their arrays alive (``data_as``).
+    def _table_args(self, table, channels: int) -> tuple:
+        return self._table(table, channels).ctypes.data_as(_vp), channels
+
+    def _weights_args(self, weights, shift: int, border: int) -> tuple:
+        w = self._weights(weights)
+        return w.ctypes.data_as(_vp), w.shape[1], w.shape[0], shift, border
+
+    def _jpeg_submit(self, name: str, fn, extra, jpegs, sizes, quality: int, subsamp: int, flags: int) -> int:
+        """Every ``jpeg_*_submit*``: stage the batch through ``fn`` and note its frame count under the
+        ticket.  ``sizes`` None: ``jpegs`` is a list of buffers; else ``jpegs`` and ``sizes`` are address
+        and size arrays (the JPEGs in a worker's ring slots)."""
+        if sizes is None:
+            n = len(jpegs)
+            if n == 0:
+                raise ValueError(f"{name}: empty batch")
+            srcs, ja = self._ptrs(jpegs)
+            js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
+        else:
+            a = np.ascontiguousarray(jpegs, np.uint64)
+            z = np.ascontiguousarray(sizes, np.uint64)
+            n = len(a)
+            if n == 0 or len(z) != n:
+                raise ValueError(f"{name}: empty batch or sizes of another length")
+            ja, js = a.ctypes.data, z.ctypes.data
+        t = ctypes.c_uint64(0)
+        self._check(fn(self._ctx, ja, js, n, *extra, quality, subsamp, flags, ctypes.byref(t)))
+        self._jpeg_n[t.value] = n
+        return t.value
+
+    def _jpeg_bench(self, fn, extra, colour: str, jpegs: Sequence, quality: int, subsamp: int, flags: int, iters: int):
+        """Every ``jpeg_bench_*``; ``colour``: the filter's name for the colour stage."""
+        n = len(jpegs)
+        srcs, ja = self._ptrs(jpegs)
+        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
+        ms = ctypes.c_float(0)
+        st = (ctypes.c_float * 8)()
+        self._check(fn(self._ctx, ja, js, n, *extra, quality, subsamp, flags, iters, ctypes.byref(ms), st))
+        names = ("unstuff", "huffman_sync", "huffman_write", "dc_idct", colour, "fdct_huffman",
+                 "stuffing", "sync_passes")
+        return ms.value, dict(zip(names, [float(x) for x in st]))
+
+    def _jpeg_take(self, ticket: int, name: str = "", outputs: Optional[int] = None) -> int:
+        """The frame count of a submitted batch, taken off the table; ``outputs`` (how many the caller
+        brought), when given, must equal it, else the ticket stays collectable."""
+        n = self._jpeg_n.pop(ticket, None)
+        if n is None:
+            raise VFilterError(f"unknown JPEG ticket {ticket}", VF_E_INVALID)
+        if outputs is not None and outputs != n:
+            self._jpeg_n[ticket] = n
+            raise ValueError(f"{name}: {outputs} outputs for a batch of {n}")
+        return n
+
     def jpeg_invert(self, jpegs: Sequence, quality: int, subsamp: int, flags: int = 0) -> list:
         """decode -> bitwise_not -> encode for every JPEG, fused on the GPU; returns bytes."""
         if len(jpegs) == 0:
@@ -626,15 +682,8 @@ class Context:
     def jpeg_invert_submit(self, jpegs: Sequence, quality: int, subsamp: int, flags: int = 0) -> int:
         """Stage the batch and queue its GPU work; returns a ticket at once (the inputs may be
         released as soon as this returns)."""
-        n = len(jpegs)
-        if n == 0:
-            raise ValueError("jpeg_invert_submit: empty batch")
-        srcs, ja = self._ptrs(jpegs)
-        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
-        t = ctypes.c_uint64(0)
-        self._check(self._lib.vf_jpeg_invert_submit(self._ctx, ja, js, n, quality, subsamp, flags, ctypes.byref(t)))
-        self.__dict__.setdefault("_jpeg_n", {})[t.value] = n
-        return t.value
+        return self._jpeg_submit("jpeg_invert_submit", self._lib.vf_jpeg_invert_submit, (), jpegs, None,
+                                 quality, subsamp, flags)
 
     def jpeg_invert_ready(self, ticket: int) -> bool:
         done = ctypes.c_int(0)
@@ -644,9 +693,7 @@ class Context:
     def jpeg_invert_result(self, ticket: int) -> list:
         """Wait for a submitted batch; returns one uint8 array view per frame, all views into
         one fresh buffer (bytes-like: they can go on the wire as they are)."""
-        n = self.__dict__.get("_jpeg_n", {}).pop(ticket, None)
-        if n is None:
-            raise VFilterError(f"unknown JPEG ticket {ticket}", VF_E_INVALID)
+        n = self._jpeg_take(ticket)
         total = ctypes.c_size_t(0)
         self._check(self._lib.vf_jpeg_invert_wait(self._ctx, ticket, ctypes.byref(total)))
         buf = np.empty(max(1, total.value), np.uint8)
@@ -660,12 +707,7 @@ class Context:
         array, e.g. the output half of the frame's ring slot) when it fits; returns per frame a
         view ``outs[i][:size]``, or, for a frame without room (or ``outs[i]`` None), a view into
         one fresh buffer holding it (vf_jpeg_invert_scatter, then a packed fetch only if needed)."""
-        n = self.__dict__.get("_jpeg_n", {}).pop(ticket, None)
-        if n is None:
-            raise VFilterError(f"unknown JPEG ticket {ticket}", VF_E_INVALID)
-        if len(outs) != n:
-            self.__dict__["_jpeg_n"][ticket] = n
-            raise ValueError(f"jpeg_invert_result_into: {len(outs)} outputs for a batch of {n}")
+        n = self._jpeg_take(ticket, "jpeg_invert_result_into", len(outs))
         total = ctypes.c_size_t(0)
         self._check(self._lib.vf_jpeg_invert_wait(self._ctx, ticket, ctypes.byref(total)))
         op = (ctypes.c_void_p * n)(*[None if o is None else o.ctypes.data for o in outs])
@@ -689,28 +731,15 @@ class Context:
     def jpeg_invert_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, quality: int, subsamp: int,
                                  flags: int = 0) -> int:
         """``jpeg_invert_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
-        a = np.ascontiguousarray(addrs, np.uint64)
-        z = np.ascontiguousarray(sizes, np.uint64)
-        n = len(a)
-        if n == 0 or len(z) != n:
-            raise ValueError("jpeg_invert_submit_addrs: empty batch or sizes of another length")
-        t = ctypes.c_uint64(0)
-        self._check(self._lib.vf_jpeg_invert_submit(self._ctx, a.ctypes.data, z.ctypes.data, n, quality, subsamp,
-                                                    flags, ctypes.byref(t)))
-        self.__dict__.setdefault("_jpeg_n", {})[t.value] = n
-        return t.value
+        return self._jpeg_submit("jpeg_invert_submit_addrs", self._lib.vf_jpeg_invert_submit, (), addrs, sizes,
+                                 quality, subsamp, flags)
 
     def jpeg_invert_result_into_addrs(self, ticket: int, out_addrs: np.ndarray, cap: int):
         """``jpeg_invert_result_into`` for outputs given as addresses of ``cap`` writable bytes each
         (the output halves of ring slots): returns (sizes int64, {i: JPEG} for the frames that did
         not fit and come back in a fresh buffer)."""
-        n = self.__dict__.get("_jpeg_n", {}).pop(ticket, None)
-        if n is None:
-            raise VFilterError(f"unknown JPEG ticket {ticket}", VF_E_INVALID)
         oa = np.ascontiguousarray(out_addrs, np.uint64)
-        if len(oa) != n:
-            self.__dict__["_jpeg_n"][ticket] = n
-            raise ValueError(f"jpeg_invert_result_into_addrs: {len(oa)} outputs for a batch of {n}")
+        n = self._jpeg_take(ticket, "jpeg_invert_result_into_addrs", len(oa))
         total = ctypes.c_size_t(0)
         self._check(self._lib.vf_jpeg_invert_wait(self._ctx, ticket, ctypes.byref(total)))
         caps = np.full(n, cap, np.uint64)
@@ -736,21 +765,13 @@ class Context:
 
     def jpeg_invert_release(self, ticket: int) -> None:
         """Drop a submitted batch without reading it."""
-        if self.__dict__.get("_jpeg_n", {}).pop(ticket, None) is not None:
+        if self._jpeg_n.pop(ticket, None) is not None:
             self._check(self._lib.vf_jpeg_invert_fetch(self._ctx, ticket, None, 0, None, None))
 
     def jpeg_bench_invert(self, jpegs: Sequence, quality: int, subsamp: int, flags: int = 0, iters: int = 10):
         """(mean ms per batch, {stage: ms}) for the GPU part of jpeg_invert on resident inputs."""
-        n = len(jpegs)
-        srcs, ja = self._ptrs(jpegs)
-        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
-        ms = ctypes.c_float(0)
-        st = (ctypes.c_float * 8)()
-        self._check(self._lib.vf_jpeg_bench_invert(self._ctx, ja, js, n, quality, subsamp, flags, iters,
-                                                   ctypes.byref(ms), st))
-        names = ("unstuff", "huffman_sync", "huffman_write", "dc_idct", "color_invert", "fdct_huffman",
-                 "stuffing", "sync_passes")
-        return ms.value, dict(zip(names, [float(x) for x in st]))
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_invert, (), "color_invert", jpegs, quality, subsamp, flags,
+                                iters)
 
     # -- JPEG with a table in place of the inversion (vf_jpeg_lut*); tickets are invert tickets ----
     def jpeg_lut(self, jpegs: Sequence, table, channels: int, quality: int, subsamp: int, flags: int = 0) -> list:
@@ -763,47 +784,20 @@ class Context:
     def jpeg_lut_submit(self, jpegs: Sequence, table, channels: int, quality: int, subsamp: int,
                         flags: int = 0) -> int:
         """``jpeg_invert_submit`` with the table; collect with the ``jpeg_invert_result*`` methods."""
-        n = len(jpegs)
-        if n == 0:
-            raise ValueError("jpeg_lut_submit: empty batch")
-        t = self._table(table, channels)
-        srcs, ja = self._ptrs(jpegs)
-        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
-        tk = ctypes.c_uint64(0)
-        self._check(self._lib.vf_jpeg_lut_submit(self._ctx, ja, js, n, t.ctypes.data, channels, quality, subsamp,
-                                                 flags, ctypes.byref(tk)))
-        self.__dict__.setdefault("_jpeg_n", {})[tk.value] = n
-        return tk.value
+        return self._jpeg_submit("jpeg_lut_submit", self._lib.vf_jpeg_lut_submit, self._table_args(table, channels),
+                                 jpegs, None, quality, subsamp, flags)
 
     def jpeg_lut_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, table, channels: int, quality: int,
                               subsamp: int, flags: int = 0) -> int:
         """``jpeg_lut_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
-        a = np.ascontiguousarray(addrs, np.uint64)
-        z = np.ascontiguousarray(sizes, np.uint64)
-        n = len(a)
-        if n == 0 or len(z) != n:
-            raise ValueError("jpeg_lut_submit_addrs: empty batch or sizes of another length")
-        t = self._table(table, channels)
-        tk = ctypes.c_uint64(0)
-        self._check(self._lib.vf_jpeg_lut_submit(self._ctx, a.ctypes.data, z.ctypes.data, n, t.ctypes.data, channels,
-                                                 quality, subsamp, flags, ctypes.byref(tk)))
-        self.__dict__.setdefault("_jpeg_n", {})[tk.value] = n
-        return tk.value
+        return self._jpeg_submit("jpeg_lut_submit_addrs", self._lib.vf_jpeg_lut_submit,
+                                 self._table_args(table, channels), addrs, sizes, quality, subsamp, flags)
 
     def jpeg_bench_lut(self, jpegs: Sequence, table, channels: int, quality: int, subsamp: int, flags: int = 0,
                        iters: int = 10):
         """``jpeg_bench_invert`` with the table in the colour stage."""
-        n = len(jpegs)
-        t = self._table(table, channels)
-        srcs, ja = self._ptrs(jpegs)
-        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
-        ms = ctypes.c_float(0)
-        st = (ctypes.c_float * 8)()
-        self._check(self._lib.vf_jpeg_bench_lut(self._ctx, ja, js, n, t.ctypes.data, channels, quality, subsamp,
-                                                flags, iters, ctypes.byref(ms), st))
-        names = ("unstuff", "huffman_sync", "huffman_write", "dc_idct", "color_lut", "fdct_huffman",
-                 "stuffing", "sync_passes")
-        return ms.value, dict(zip(names, [float(x) for x in st]))
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_lut, self._table_args(table, channels), "color_lut", jpegs,
+                                quality, subsamp, flags, iters)
 
     # -- JPEG with a convolution in place of the inversion (vf_jpeg_conv*); tickets are invert tickets ----
     def jpeg_conv(self, jpegs: Sequence, weights, shift: int, border: int, quality: int, subsamp: int,
@@ -817,48 +811,21 @@ class Context:
     def jpeg_conv_submit(self, jpegs: Sequence, weights, shift: int, border: int, quality: int, subsamp: int,
                          flags: int = 0) -> int:
         """``jpeg_invert_submit`` with the kernel; collect with the ``jpeg_invert_result*`` methods."""
-        n = len(jpegs)
-        if n == 0:
-            raise ValueError("jpeg_conv_submit: empty batch")
-        w = self._weights(weights)
-        srcs, ja = self._ptrs(jpegs)
-        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
-        tk = ctypes.c_uint64(0)
-        self._check(self._lib.vf_jpeg_conv_submit(self._ctx, ja, js, n, w.ctypes.data, w.shape[1], w.shape[0], shift,
-                                                  border, quality, subsamp, flags, ctypes.byref(tk)))
-        self.__dict__.setdefault("_jpeg_n", {})[tk.value] = n
-        return tk.value
+        return self._jpeg_submit("jpeg_conv_submit", self._lib.vf_jpeg_conv_submit,
+                                 self._weights_args(weights, shift, border), jpegs, None, quality, subsamp, flags)
 
     def jpeg_conv_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, weights, shift: int, border: int,
                                quality: int, subsamp: int, flags: int = 0) -> int:
         """``jpeg_conv_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
-        a = np.ascontiguousarray(addrs, np.uint64)
-        z = np.ascontiguousarray(sizes, np.uint64)
-        n = len(a)
-        if n == 0 or len(z) != n:
-            raise ValueError("jpeg_conv_submit_addrs: empty batch or sizes of another length")
-        w = self._weights(weights)
-        tk = ctypes.c_uint64(0)
-        self._check(self._lib.vf_jpeg_conv_submit(self._ctx, a.ctypes.data, z.ctypes.data, n, w.ctypes.data, w.shape[1],
-                                                  w.shape[0], shift, border, quality, subsamp, flags, ctypes.byref(tk)))
-        self.__dict__.setdefault("_jpeg_n", {})[tk.value] = n
-        return tk.value
+        return self._jpeg_submit("jpeg_conv_submit_addrs", self._lib.vf_jpeg_conv_submit,
+                                 self._weights_args(weights, shift, border), addrs, sizes, quality, subsamp, flags)
 
     def jpeg_bench_conv(self, jpegs: Sequence, weights, shift: int, border: int, quality: int, subsamp: int,
                         flags: int = 0, iters: int = 10):
         """``jpeg_bench_invert`` with the convolution between the decode and the encode (its time is
         in the total, not in a stage: it runs between the colour and the fdct stage events)."""
-        n = len(jpegs)
-        w = self._weights(weights)
-        srcs, ja = self._ptrs(jpegs)
-        js = (ctypes.c_size_t * n)(*[s.nbytes for s in srcs])
-        ms = ctypes.c_float(0)
-        st = (ctypes.c_float * 8)()
-        self._check(self._lib.vf_jpeg_bench_conv(self._ctx, ja, js, n, w.ctypes.data, w.shape[1], w.shape[0], shift,
-                                                 border, quality, subsamp, flags, iters, ctypes.byref(ms), st))
-        names = ("unstuff", "huffman_sync", "huffman_write", "dc_idct", "color", "fdct_huffman",
-                 "stuffing", "sync_passes")
-        return ms.value, dict(zip(names, [float(x) for x in st]))
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_conv, self._weights_args(weights, shift, border), "color",
+                                jpegs, quality, subsamp, flags, iters)
 
 
 def jpeg_header(jpeg) -> tuple:

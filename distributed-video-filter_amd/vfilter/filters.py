@@ -8,6 +8,7 @@ there is no CPU fallback.
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 from typing import List, Optional, Sequence
 
@@ -192,6 +193,57 @@ def as_kernel(kernel) -> tuple:
     if w.size and (int(w.max()) > 32767 or int(w.min()) < -32768):
         raise ValueError("filter2d: a weight does not fit 16 bits")
     return np.ascontiguousarray(w, dtype=np.int16), shift
+
+
+# -- a batch's filter as one value (TurboJPEG.filter_*, the workers) ------------------------------
+# Immutable and validated when constructed, so a bad table or kernel is refused before any GPU
+# work.  ``family`` names the methods the value goes through -- ``Context.jpeg_<family>``,
+# ``jpeg_<family>_submit``, ``jpeg_<family>_submit_addrs`` -- and ``args`` are the arguments those
+# take between the batch and the quality.  This is the one place that pairs the two.
+
+@dataclasses.dataclass(frozen=True)
+class Invert:
+    """``cv2.bitwise_not`` (inverter.py:41)."""
+    family = "invert"
+    args = ()
+
+
+@dataclasses.dataclass(frozen=True, init=False)
+class Table:
+    """``cv2.LUT`` with ``table`` (as for ``lut``), copied: the caller may change its array at once."""
+    planar: bytes
+    channels: int
+    family = "lut"
+
+    def __init__(self, table):
+        planar, channels = as_table(table)
+        object.__setattr__(self, "planar", planar)
+        object.__setattr__(self, "channels", channels)
+
+    @property
+    def args(self) -> tuple:
+        return self.planar, self.channels
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Kernel:
+    """``cv2.filter2D`` with ``kernel`` and ``border`` (as for ``filter2d``), copied."""
+    weights: np.ndarray  # int16 kh x kw, read-only
+    shift: int
+    border: str
+    border_code: int
+    family = "conv"
+
+    def __init__(self, kernel, border: str = "reflect101"):
+        weights, shift = as_kernel(kernel)
+        weights.flags.writeable = False
+        fields = {"weights": weights, "shift": shift, "border": border, "border_code": border_code(border)}
+        for name, v in fields.items():
+            object.__setattr__(self, name, v)
+
+    @property
+    def args(self) -> tuple:
+        return self.weights, self.shift, self.border_code
 
 
 def _conv_frame(name: str, a) -> np.ndarray:

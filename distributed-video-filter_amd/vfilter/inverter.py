@@ -31,6 +31,7 @@ import numpy as np
 
 from . import wire
 from ._lib import Context, default_device
+from .filters import Invert
 from .jpeg import TurboJPEG
 from .worker import RingResults, Worker, WorkerFailed, ring_results
 
@@ -48,11 +49,33 @@ def auto_credit(mean_jpeg_bytes: float) -> int:
     return SMALL_CREDIT if 0 < mean_jpeg_bytes <= SMALL_JPEG_BYTES else CREDIT
 
 
+def ring_input_addresses(ring, cols) -> Optional[np.ndarray]:
+    """The addresses of a batch's frames in ``ring`` (the input halves of their slots), or None when
+    a record lies outside this ring slice.  This is the one place where a Python integer becomes
+    an address the library dereferences: a record that fails here never becomes a raw GPU address
+    (the caller takes the per-frame views path, which refuses it)."""
+    sb = ring.slot_bytes
+    slots, nbs = cols["slot"], cols["nbytes"]
+    if len(slots) and (int(slots.min()) < 0 or int(slots.max()) >= ring.nslots or int(nbs.min()) < 0
+                       or int(nbs.max()) > sb):
+        return None
+    return np.uint64(ring.base_address) + slots.astype(np.uint64) * np.uint64(2 * sb)
+
+
 class InverterWorker(Worker):
+    # What a worker with another filter does differently (FilterWorker below), each a piece to override:
+    # JPEG mode with delay > 0.  False: leave the fused pass and run the reference's shape per frame
+    # (decode, sleep, invert_host, encode).  True: sleep delay * len(frames) once, then the fused batch.
+    fused_with_delay = False
+    # Raw mode.  True: batches are queued on the context's engine ("gpu" / "gpu_ring" handles).
+    # False: they run synchronously in process_batch and submit_ring_batch returns None.
+    raw_async = True
+
     def __init__(self, host: str = "localhost", distribute_port: int = 5555, collect_port: int = 5556,
                  delay: float = 0.0, use_jpeg: bool = True, *, device: Optional[int] = None,
                  max_frame_bytes: int = 3840 * 2160 * 3, install_signal_handlers: bool = True,
-                 tj_version: int = 3, **worker_kw):
+                 tj_version: int = 3, filter=None, **worker_kw):
+        self.filter = filter if filter is not None else Invert()  # the JPEG path's filter (vfilter.filters)
         # batches in progress at once: raw, batch i on the GPU while batch i+1 is received;
         # JPEG, three, since the kernels of batches on separate codecs overlap (1080p worker
         # form 24.6 k fps with 3 in flight vs 21.4 k with 2: profiles/r02_jpeg_depth.jsonl)
@@ -88,10 +111,19 @@ class InverterWorker(Worker):
             print(f"\nReceived signal {signum}, shutting down...")
             self.running = False
 
+    def _fused(self) -> bool:
+        """JPEG frames go through the fused GPU pass (decode -> filter -> encode, TurboJPEG.filter_*)."""
+        return self.jpeg is not None and (self.delay <= 0 or self.fused_with_delay)
+
     # -- one frame (inverter.py:29-46) ------------------------------------------------------
     def __call__(self, frame_bytes):
-        if self.jpeg and self.delay <= 0:
-            return self.jpeg.invert(frame_bytes)                    # inverter.py:32 -> :41 -> :44, fused
+        if not self._fused():
+            return self.unfused_call(frame_bytes)
+        if self.delay > 0:                                          # inverter.py:37-38
+            time.sleep(self.delay)
+        return self.jpeg.filter_batch([frame_bytes], self.filter)[0]  # inverter.py:32 -> :41 -> :44, fused
+
+    def unfused_call(self, frame_bytes):
         if self.jpeg:
             frame = self.jpeg.decode(frame_bytes)                   # inverter.py:32
         else:
@@ -107,49 +139,57 @@ class InverterWorker(Worker):
 
     # -- a dispatched batch: one gathered device call ------------------------------------
     def process_batch(self, frames: Sequence, metas: Sequence[wire.FrameMeta], outs: Sequence) -> List:
-        if self.jpeg and self.delay <= 0:
-            # the whole batch in one fused GPU pass; results are JPEGs of their own size (the
-            # loop puts ring frames' results into their slots, see Worker._finish_job)
-            try:
-                return self.jpeg.invert_batch(list(frames))
-            except Exception:  # retry frame by frame so a bad frame fails alone (worker.py:74-76)
-                return super().process_batch(frames, metas, outs)
-        if self.jpeg:
+        if self.jpeg and not self._fused():
             return super().process_batch(frames, metas, outs)
         if self.delay > 0:
             time.sleep(self.delay * len(frames))
-        srcs, dsts, sizes, results = [], [], [], []
+        if self.jpeg:
+            # the whole batch in one fused GPU pass; results are JPEGs of their own size (the
+            # loop puts ring frames' results into their slots, see Worker._finish_job)
+            try:
+                return self.jpeg.filter_batch(frames, self.filter)
+            except Exception:  # retry frame by frame so a bad frame fails alone (worker.py:74-76)
+                return self._frame_by_frame(frames, metas, outs)
+        srcs, dsts = [], []
         for f, o in zip(frames, outs):
             src = f if isinstance(f, np.ndarray) else np.frombuffer(f, dtype=np.uint8)
-            dst = o if o is not None else np.empty(src.nbytes, np.uint8)
             srcs.append(src)
-            dsts.append(dst)
-            sizes.append(src.nbytes)
-            results.append(dst)
+            dsts.append(o if o is not None else np.empty(src.nbytes, np.uint8))
+        return self.process_raw_batch(frames, metas, outs, srcs, dsts)
+
+    def process_raw_batch(self, frames, metas, outs, srcs: List[np.ndarray], dsts: List[np.ndarray]) -> List:
+        """The raw half of process_batch: ``srcs`` and ``dsts`` are the frames and their outputs as arrays."""
         t_call = time.time()
         try:
-            self.ctx.invert_frames_host(srcs, dsts, sizes)
+            self.ctx.invert_frames_host(srcs, dsts, [s.nbytes for s in srcs])
         except Exception as e:
             return [e] * len(frames)
         self.last_spans = gpu_spans(self.ctx.last_timeline(), t_call)
-        return results
+        return dsts
+
+    def _frame_by_frame(self, frames, metas, outs) -> List:
+        delay, self.delay = self.delay, 0.0  # already slept for the batch
+        try:
+            return Worker.process_batch(self, frames, metas, outs)
+        finally:
+            self.delay = delay
 
     # -- asynchronous submission ---------------------------------------------------------
     def submit_batch(self, frames: Sequence, metas: Sequence[wire.FrameMeta], outs: Sequence):
         """Queue the batch with vf_invert_frames_async and return to receiving at once: the
         context's engine thread streams consecutive batches through the GPU back to back.
         Ring frames (page-locked) are inverted in place (zero-copy); socket payloads are staged.
-        JPEG batches are queued on a codec of their own (vf_jpeg_invert_submit: fused decode ->
-        invert -> encode) and collected later, ring frames' results straight into their slots."""
+        JPEG batches are queued on a codec of their own (vf_jpeg_*_submit: fused decode ->
+        filter -> encode) and collected later, ring frames' results straight into their slots."""
         if self.jpeg:
             self._note_jpeg_bytes(float(sum(len(f) for f in frames)), len(frames))
         if self.jpeg and self.delay <= 0:
             try:  # staged and queued now; the loop receives the next batch while this one runs
-                return ("jpeg", self.jpeg.invert_batch_submit(list(frames)), list(frames), list(outs))
+                return ("jpeg", self.jpeg.filter_batch_submit(frames, self.filter), list(frames), list(outs))
             except Exception:  # a frame the host parser refuses: frame by frame (worker.py:74-76)
-                return ("done", super().process_batch(frames, metas, outs), [])
-        if self.jpeg or self.delay > 0:
-            return super().submit_batch(frames, metas, outs)
+                return ("done", self._frame_by_frame(frames, metas, outs), [])
+        if self.jpeg or self.delay > 0 or not self.raw_async:
+            return super().submit_batch(frames, metas, outs)  # synchronous: process_batch now
         srcs, dsts = [], []
         for f, o in zip(frames, outs):
             src = f if isinstance(f, np.ndarray) else np.frombuffer(f, dtype=np.uint8)
@@ -175,19 +215,17 @@ class InverterWorker(Worker):
         no ndarray per frame (at 512 x 512 JPEG, 60-80 k frames/s, the per-frame Python of the
         view path was the worker's bound).  Raw: one zero-copy launch over the slots; JPEG: one
         fused codec batch whose results are scattered into the slots' output halves."""
-        if self.delay > 0:
+        if self.delay > 0 or not (self.jpeg or self.raw_async):
+            return None  # the per-frame views path: submit_batch
+        ina = ring_input_addresses(ring, cols)
+        if ina is None:
             return None
         sb = ring.slot_bytes
-        slots, nbs = cols["slot"], cols["nbytes"]
-        if len(slots) and (int(slots.min()) < 0 or int(slots.max()) >= ring.nslots or int(nbs.min()) < 0
-                           or int(nbs.max()) > sb):
-            return None  # a record outside this ring slice: never a raw GPU address; the views path
-        ina = np.uint64(ring.base_address) + cols["slot"].astype(np.uint64) * np.uint64(2 * sb)
         nb = cols["nbytes"]
         if self.jpeg:
             self._note_jpeg_bytes(float(nb.sum()), len(nb))
             try:
-                t = self.jpeg.invert_batch_submit_addrs(ina, nb)
+                t = self.jpeg.filter_batch_submit_addrs(ina, nb, self.filter)
             except Exception:  # a frame the host parser refuses: the per-frame views path
                 return None
             return ("jpeg_ring", t, ina + np.uint64(sb), sb, ring, cols)
@@ -268,6 +306,34 @@ class InverterWorker(Worker):
         self.ctx.close()
 
 
+class FilterWorker(InverterWorker):
+    """An InverterWorker whose ``filter`` is not the inversion (LutWorker, ConvWorker).  The JPEG half
+    is InverterWorker's; a subclass adds ``raw_batch``, its filter on raw frames, which runs
+    synchronously: a batch in process_batch, and one that fails again frame by frame so that a bad
+    frame fails alone."""
+    fused_with_delay = True
+    raw_async = False
+
+    def raw_batch(self, srcs: List[np.ndarray], metas: Sequence, dsts: List[np.ndarray]) -> None:
+        """Filter the raw frames ``srcs`` into ``dsts``; ``metas[i]`` is frame i's wire metadata or None."""
+        raise NotImplementedError
+
+    def unfused_call(self, frame_bytes):
+        if self.delay > 0:                                          # inverter.py:37-38
+            time.sleep(self.delay)
+        frame = np.frombuffer(frame_bytes, dtype=np.uint8)          # inverter.py:34
+        out = np.empty_like(frame)
+        self.raw_batch([frame], [None], [out])
+        return out
+
+    def process_raw_batch(self, frames, metas, outs, srcs, dsts) -> List:
+        try:
+            self.raw_batch(srcs, metas, dsts)
+        except Exception:  # e.g. a frame that is not whole pixels, or of another size: it fails alone
+            return self._frame_by_frame(frames, metas, outs)
+        return dsts
+
+
 def gpu_spans(timeline, t_call: float) -> List[dict]:
     """Per-chunk {H2D, kernel, D2H} spans in wall-clock seconds: the call's start event is
     taken as ``t_call`` (the host time just before the call)."""
@@ -300,9 +366,10 @@ def pin_to_gpu_node(device=None) -> bool:
     return True
 
 
-def main(argv=None):
-    """inverter.py:48-61 plus the GPU worker's knobs."""
-    ap = argparse.ArgumentParser(description="Inverter worker for video processing (MI355X backend)")
+def worker_main(ap: argparse.ArgumentParser, argv, name: str, cls, own=lambda args: {}):
+    """The command line every worker shares: adds the common options to ``ap`` (which holds the
+    worker's own), parses, builds ``cls`` with the keyword arguments ``own(args)`` adds -- ``own``
+    also refuses bad values of the worker's options, before a GPU context exists -- and runs it."""
     ap.add_argument("--distribute-port", type=int, default=5555,
                     help="Port to request frames from webcam app (default: 5555)")
     ap.add_argument("--collect-port", type=int, default=5556,
@@ -312,7 +379,6 @@ def main(argv=None):
     ap.add_argument("--host", default="localhost", help="distributor host (reference: hard-coded localhost)")
     ap.add_argument("--raw", action="store_true",
                     help="raw H x W x 3 frames (use_jpeg=False); default JPEG frames, as the reference CLI")
-    ap.add_argument("--jpeg", action="store_true", help=argparse.SUPPRESS)  # the default; kept for old scripts
     ap.add_argument("--device", type=int, default=None, help="GPU ordinal (default: VF_DEVICE / LOCAL_RANK / 0)")
     ap.add_argument("--batch", type=int, default=0,
                     help="frames per request (protocol v1); default 0: JPEG 64 while the frames average "
@@ -325,17 +391,25 @@ def main(argv=None):
     ap.add_argument("--transport", choices=("auto", "zmq", "tcp"), default="auto")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args(argv)
+    kw = own(args)
     pin_to_gpu_node(args.device)
-    worker = InverterWorker(args.host, args.distribute_port, args.collect_port, args.delay,
-                            use_jpeg=not args.raw, device=args.device, batch=args.batch, inflight=args.inflight,
-                            protocol=args.protocol, transport=args.transport, verbose=args.verbose)
+    worker = cls(args.host, args.distribute_port, args.collect_port, args.delay, use_jpeg=not args.raw,
+                 device=args.device, batch=args.batch, inflight=args.inflight, protocol=args.protocol,
+                 transport=args.transport, verbose=args.verbose, **kw)
     try:
         worker.start()
     except WorkerFailed as e:  # a fresh process, not a re-exec: let the supervisor restart it
-        print(f"Inverter worker: giving up: {e}")
+        print(f"{name}: giving up: {e}")
         raise SystemExit(3)
     finally:
         worker.close()
+
+
+def main(argv=None):
+    """inverter.py:48-61 plus the GPU worker's knobs."""
+    ap = argparse.ArgumentParser(description="Inverter worker for video processing (MI355X backend)")
+    ap.add_argument("--jpeg", action="store_true", help=argparse.SUPPRESS)  # the default; kept for old scripts
+    worker_main(ap, argv, "Inverter worker", InverterWorker)
 
 
 if __name__ == "__main__":

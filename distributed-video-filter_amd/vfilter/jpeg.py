@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import as_kernel, as_table, border_code
+from .filters import Invert, Kernel, Table
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -94,53 +94,65 @@ class TurboJPEG:
         return self.ctx.jpeg_encode(list(imgs), pixel_format, quality, jpeg_subsample,
                                     self._enc_flags(flags, quality))
 
+    # One filter value (``vfilter.filters``: Invert, Table, Kernel) between decode and encode.  The
+    # ``invert*``, ``lut*`` and ``filter2d*`` methods below are these three with their filter built
+    # from the call's own arguments.
+    def filter_batch(self, jpeg_bufs: Sequence, filt, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                     flags: int = 0) -> List[bytes]:
+        """One GPU pass over the batch (safe to call from several threads at once: each call leases
+        its own codec)."""
+        run = getattr(self.ctx, "jpeg_" + filt.family)
+        return run(list(jpeg_bufs), *filt.args, quality, jpeg_subsample, self._enc_flags(flags, quality))
+
+    def filter_batch_submit(self, jpeg_bufs: Sequence, filt, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                            flags: int = 0) -> int:
+        """filter_batch, asynchronously: stage and queue the batch, return a ticket at once, to be
+        collected with the ``invert_batch_result*`` methods.  One host thread can keep several
+        batches in flight (each holds its own codec)."""
+        run = getattr(self.ctx, f"jpeg_{filt.family}_submit")
+        return run(list(jpeg_bufs), *filt.args, quality, jpeg_subsample, self._enc_flags(flags, quality))
+
+    def filter_batch_submit_addrs(self, addrs, sizes, filt, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                                  flags: int = 0) -> int:
+        """``filter_batch_submit`` for JPEGs given by address and size arrays (a worker's ring
+        slots; the memory stays valid until the result is collected)."""
+        run = getattr(self.ctx, f"jpeg_{filt.family}_submit_addrs")
+        return run(addrs, sizes, *filt.args, quality, jpeg_subsample, self._enc_flags(flags, quality))
+
     def invert(self, jpeg_buf, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
         """``encode(bitwise_not(decode(jpeg_buf)))`` (inverter.py:32 -> :41 -> :44) fused on the GPU."""
-        return self.invert_batch([jpeg_buf], quality, jpeg_subsample, flags)[0]
+        return self.filter_batch([jpeg_buf], Invert(), quality, jpeg_subsample, flags)[0]
 
     def invert_batch(self, jpeg_bufs: Sequence, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
                      flags: int = 0) -> List[bytes]:
-        """One fused GPU pass over the batch (safe to call from several threads at once: each
-        call leases its own codec)."""
-        return self.ctx.jpeg_invert(list(jpeg_bufs), quality, jpeg_subsample, self._enc_flags(flags, quality))
+        return self.filter_batch(jpeg_bufs, Invert(), quality, jpeg_subsample, flags)
 
     def invert_batch_submit(self, jpeg_bufs: Sequence, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
                             flags: int = 0) -> int:
-        """invert_batch, asynchronously: stage and queue the batch, return a ticket at once.
-        One host thread can keep several batches in flight (each holds its own codec)."""
-        return self.ctx.jpeg_invert_submit(list(jpeg_bufs), quality, jpeg_subsample, self._enc_flags(flags, quality))
+        return self.filter_batch_submit(jpeg_bufs, Invert(), quality, jpeg_subsample, flags)
 
     def invert_batch_submit_addrs(self, addrs, sizes, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
                                   flags: int = 0) -> int:
-        """``invert_batch_submit`` for JPEGs given by address and size arrays (a worker's ring
-        slots; the memory stays valid until the result is collected)."""
-        return self.ctx.jpeg_invert_submit_addrs(addrs, sizes, quality, jpeg_subsample, self._enc_flags(flags, quality))
+        return self.filter_batch_submit_addrs(addrs, sizes, Invert(), quality, jpeg_subsample, flags)
 
     # -- any other per-pixel filter: a 256-entry table (cv2.LUT) between decode and encode ----------
     def lut(self, jpeg_buf, table, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
         """``encode(cv2.LUT(decode(jpeg_buf), table))`` fused on the GPU.  ``table`` as for
         ``vfilter.lut``; a 3-channel table's channel c is channel c of the decoded BGR frame."""
-        return self.lut_batch([jpeg_buf], table, quality, jpeg_subsample, flags)[0]
+        return self.filter_batch([jpeg_buf], Table(table), quality, jpeg_subsample, flags)[0]
 
     def lut_batch(self, jpeg_bufs: Sequence, table, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
                   flags: int = 0) -> List[bytes]:
-        planar, channels = as_table(table)
-        return self.ctx.jpeg_lut(list(jpeg_bufs), planar, channels, quality, jpeg_subsample,
-                                 self._enc_flags(flags, quality))
+        return self.filter_batch(jpeg_bufs, Table(table), quality, jpeg_subsample, flags)
 
     def lut_batch_submit(self, jpeg_bufs: Sequence, table, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
                          flags: int = 0) -> int:
-        """lut_batch, asynchronously; the ticket is collected with the ``invert_batch_result*``
-        methods (the table is copied: the caller may change it at once)."""
-        planar, channels = as_table(table)
-        return self.ctx.jpeg_lut_submit(list(jpeg_bufs), planar, channels, quality, jpeg_subsample,
-                                        self._enc_flags(flags, quality))
+        """The table is copied: the caller may change it at once."""
+        return self.filter_batch_submit(jpeg_bufs, Table(table), quality, jpeg_subsample, flags)
 
     def lut_batch_submit_addrs(self, addrs, sizes, table, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
                                flags: int = 0) -> int:
-        planar, channels = as_table(table)
-        return self.ctx.jpeg_lut_submit_addrs(addrs, sizes, planar, channels, quality, jpeg_subsample,
-                                              self._enc_flags(flags, quality))
+        return self.filter_batch_submit_addrs(addrs, sizes, Table(table), quality, jpeg_subsample, flags)
 
     # -- a neighbourhood filter: cv2.filter2D between decode and encode --------------------------------
     def filter2d(self, jpeg_buf, kernel, border: str = "reflect101", quality: int = 85,
@@ -148,27 +160,20 @@ class TurboJPEG:
         """``encode(cv2.filter2D(decode(jpeg_buf), -1, kernel))`` on the GPU, the pixels never leaving
         it.  ``kernel`` and ``border`` as for ``vfilter.filter2d``; the kernel is applied to each
         channel of the decoded BGR frame."""
-        return self.filter2d_batch([jpeg_buf], kernel, border, quality, jpeg_subsample, flags)[0]
+        return self.filter_batch([jpeg_buf], Kernel(kernel, border), quality, jpeg_subsample, flags)[0]
 
     def filter2d_batch(self, jpeg_bufs: Sequence, kernel, border: str = "reflect101", quality: int = 85,
                        jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
-        weights, shift = as_kernel(kernel)
-        return self.ctx.jpeg_conv(list(jpeg_bufs), weights, shift, border_code(border), quality, jpeg_subsample,
-                                  self._enc_flags(flags, quality))
+        return self.filter_batch(jpeg_bufs, Kernel(kernel, border), quality, jpeg_subsample, flags)
 
     def filter2d_batch_submit(self, jpeg_bufs: Sequence, kernel, border: str = "reflect101", quality: int = 85,
                               jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> int:
-        """filter2d_batch, asynchronously; the ticket is collected with the ``invert_batch_result*``
-        methods (the kernel is copied: the caller may change it at once)."""
-        weights, shift = as_kernel(kernel)
-        return self.ctx.jpeg_conv_submit(list(jpeg_bufs), weights, shift, border_code(border), quality,
-                                         jpeg_subsample, self._enc_flags(flags, quality))
+        """The kernel is copied: the caller may change it at once."""
+        return self.filter_batch_submit(jpeg_bufs, Kernel(kernel, border), quality, jpeg_subsample, flags)
 
     def filter2d_batch_submit_addrs(self, addrs, sizes, kernel, border: str = "reflect101", quality: int = 85,
                                     jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> int:
-        weights, shift = as_kernel(kernel)
-        return self.ctx.jpeg_conv_submit_addrs(addrs, sizes, weights, shift, border_code(border), quality,
-                                               jpeg_subsample, self._enc_flags(flags, quality))
+        return self.filter_batch_submit_addrs(addrs, sizes, Kernel(kernel, border), quality, jpeg_subsample, flags)
 
     def invert_batch_result_into_addrs(self, ticket: int, out_addrs, cap: int):
         """(sizes, {i: JPEG that did not fit}): each result written at ``out_addrs[i]`` (``cap``

@@ -159,6 +159,72 @@ def test_lut_worker_jpeg_and_raw(jpegs):
         w.close()
 
 
+def test_ring_batches_of_all_three_workers(jpegs):
+    """``submit_ring_batch`` -> ``poll_batch`` on the "jpeg_ring" handle: JPEGs read from ring slots by
+    address, results written into the slots' output halves.  A record outside the ring, a raw table or
+    kernel worker and a worker with a delay all decline (None: the loop takes the per-frame views path)."""
+    import _conv_ref as R
+    from vfilter import shm, wire
+    from vfilter.conv_worker import ConvWorker
+    from vfilter.inverter import InverterWorker
+    from vfilter.lut_worker import LutWorker
+    from vfilter.worker import RingResults
+    kern = R.kernel_set()["random3x5"]
+    ins = [jpegs[BIG], jpegs[3], jpegs[-1]]  # 250 x 130 4:2:2, 17 x 13 4:2:0, 33 x 17 grey
+    wants = {
+        InverterWorker: [J.invert_jpeg(j) for j in ins],
+        LutWorker: [want(j, T3) for j in ins],
+        ConvWorker: [J.encode(R.filter2d(J.decode(j, J.TJPF_BGR), kern[0], kern[1], "reflect101"), 85, J.TJPF_BGR,
+                              J.TJSAMP_422) for j in ins],
+    }
+    own = {InverterWorker: {}, LutWorker: {"table": T3}, ConvWorker: {"kernel": kern}}
+    kw = dict(install_signal_handlers=False, transport="tcp")
+    ring = shm.FrameRing(nslots=4, slot_bytes=65536)
+    workers = []
+
+    def make(cls, delay=0.0, use_jpeg=True):
+        w = cls("127.0.0.1", 1, 1, delay, use_jpeg=use_jpeg, **own[cls], **kw)
+        workers.append(w)
+        w.on_ring_attached(ring)
+        return w
+
+    def done(w):
+        workers.remove(w)
+        w.close()  # also takes the ring's page-lock back, for the next worker's context
+
+    try:
+        cols = np.zeros(3, wire.COLS)
+        for i, (slot, j) in enumerate(zip((0, 1, 3), ins)):
+            assert len(j) <= ring.slot_bytes
+            ring.in_view(slot, len(j))[:] = np.frombuffer(j, np.uint8)
+            cols[i] = (i, len(j), slot, 0, (0, 0, 0, 0))
+        for cls in (InverterWorker, LutWorker, ConvWorker):
+            w = make(cls)
+            for slot in (0, 1, 3):
+                ring.out_view(slot, ring.slot_bytes)[:] = 0  # nothing left of the worker before
+            h = w.submit_ring_batch(ring, cols)
+            assert h is not None and h[0] == "jpeg_ring", cls
+            res, _ = w.poll_batch(h, True)
+            assert isinstance(res, RingResults) and not res.errors and not res.overflow, cls
+            for i, wanted in enumerate(wants[cls]):
+                assert int(res.nbytes[i]) == len(wanted), (cls, i)
+                assert ring.out_view(int(cols["slot"][i]), int(res.nbytes[i])).tobytes() == wanted, (cls, i)
+            for field, value in (("slot", 4), ("slot", -1), ("nbytes", ring.slot_bytes + 1)):
+                bad = cols.copy()
+                bad[field][1] = value
+                assert w.submit_ring_batch(ring, bad) is None, (cls, field, value)
+            done(w)
+        for cls, delay, use_jpeg in ((LutWorker, 0.0, False), (ConvWorker, 0.0, False), (InverterWorker, 0.001, True),
+                                     (LutWorker, 0.001, True), (ConvWorker, 0.001, True)):
+            w = make(cls, delay, use_jpeg)
+            assert w.submit_ring_batch(ring, cols) is None, (cls, delay, use_jpeg)
+            done(w)
+    finally:
+        for w in workers:
+            w.close()
+        ring.close()
+
+
 def test_invert_is_unchanged_after_lut_calls(tj, jpegs):
     j = jpegs[BIG]
     assert tj.lut(j, T3) == want(j, T3)
