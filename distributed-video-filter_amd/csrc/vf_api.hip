@@ -513,17 +513,19 @@ VF_EXPORT int vf_conv_device(vf_ctx *ctx, const void *dsrc, void *ddst, int widt
   return VF_OK;
 }
 
-VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
-                                  const int *heights, int n, int channels, const int16_t *weights, int kw, int kh,
-                                  int shift, int border) {
-  VF_CHECK_CTX(ctx);
-  const char *fn = "vf_conv_frames_host";
-  int rc = check_kernel(ctx, fn, weights, kw, kh, shift, border);
-  if (rc != VF_OK) return rc;
+namespace {
+
+// The host path of the neighbourhood filters (vf_conv_frames_host, vf_rank_frames_host): the
+// frames' checks, the bands (vf_conv_bands.h) for a filter of vertical radius ry, and per fill of
+// the staging buffers upload, launch(din, dout, frame, band, stream), download, wait.
+template <class Launch>
+int neighbour_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs, uint8_t *const *dsts,
+                          const int *widths, const int *heights, int n, int channels, int ry, Launch &&launch) {
   if (channels != 1 && channels != 3)
     return set_err(ctx, VF_E_INVALID, 0, "%s: channels=%d, a frame has 1 or 3", fn, channels);
   if (n < 0) return set_err(ctx, VF_E_INVALID, 0, "%s: n < 0", fn);
   if (n > 0 && (!srcs || !dsts || !widths || !heights)) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL array", fn);
+  int rc;
   // one upload + launch + download per band (vf_conv_bands.h); most frames are one band
   struct Piece {
     int frame;
@@ -533,7 +535,6 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
   std::vector<Piece> pieces;
   std::vector<std::vector<uint8_t>> saved;
   const size_t cap = ctx->raw_cap;
-  const int ry = kh / 2;
   for (int i = 0; i < n; ++i) {
     if (widths[i] == 0 && heights[i] == 0) continue;  // the empty frame
     if ((rc = check_frame_shape(ctx, fn, widths[i], heights[i], channels)) != VF_OK) return rc;
@@ -560,7 +561,6 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
   const size_t alloc = ((cap + 15 + 15) & ~(size_t)15);
   if ((rc = raw_staging(ctx, fn, alloc)) != VF_OK) return rc;
   hipStream_t st = ctx->raw_stream;
-  const int form = vf::conv_form_env();
   std::vector<size_t> at(pieces.size());
   for (size_t i = 0; i < pieces.size();) {
     // one fill of the buffers: upload and filter the bands that fit, download them, wait
@@ -578,8 +578,7 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
         VF_HIP(ctx, hipMemcpyAsync(din, p.halo, head, hipMemcpyHostToDevice, st));
       }
       VF_HIP(ctx, hipMemcpyAsync(din + head, src + (size_t)p.b.s0 * row + head, in_bytes - head, hipMemcpyHostToDevice, st));
-      VF_HIP(ctx, vf::launch_conv(din, dout, widths[p.frame], channels, heights[p.frame], p.b.y0, p.b.y1 - p.b.y0, p.b.s0,
-                                  p.b.s1 - p.b.s0, weights, kw, kh, shift, border, form, st));
+      VF_HIP(ctx, launch(din, dout, widths[p.frame], heights[p.frame], p.b, st));
       at[j] = cout;
       cin += (in_bytes + 15) & ~(size_t)15;
       cout += (out_bytes + 15) & ~(size_t)15;
@@ -594,6 +593,90 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
     i = j;
   }
   return VF_OK;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                  const int *heights, int n, int channels, const int16_t *weights, int kw, int kh,
+                                  int shift, int border) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_conv_frames_host";
+  const int rc = check_kernel(ctx, fn, weights, kw, kh, shift, border);
+  if (rc != VF_OK) return rc;
+  const int form = vf::conv_form_env();
+  return neighbour_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, kh / 2,
+                               [&](const uint8_t *din, uint8_t *dout, int w, int h, const vf::conv::Band &b, hipStream_t st) {
+                                 return vf::launch_conv(din, dout, w, channels, h, b.y0, b.y1 - b.y0, b.s0, b.s1 - b.s0,
+                                                        weights, kw, kh, shift, border, form, st);
+                               });
+}
+
+// ---- rank filters (cv2.erode, cv2.dilate, cv2.medianBlur) on raw frames ---------------------------
+
+namespace {
+
+// The filter arguments every vf_rank_* / vf_jpeg_rank* entry point shares; *mask: the element's
+// members, bit j * kw + i.
+int check_rank(vf_ctx *ctx, const char *fn, int op, const uint8_t *element, int kw, int kh, int border, uint64_t *mask) {
+  if (op != VF_RANK_ERODE && op != VF_RANK_DILATE && op != VF_RANK_MEDIAN)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: unknown op %d", fn, op);
+  if (!element) return set_err(ctx, VF_E_INVALID, 0, "%s: element is NULL", fn);
+  if (kw < 1 || kh < 1 || kw > vf::conv::kMaxK || kh > vf::conv::kMaxK || !(kw & 1) || !(kh & 1))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: a %d x %d element; sides are odd and at most %d", fn, kw, kh,
+                   vf::conv::kMaxK);
+  if (border != VF_BORDER_REFLECT101 && border != VF_BORDER_REPLICATE && border != VF_BORDER_CONSTANT)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: unknown border %d", fn, border);
+  *mask = vf::rank_mask(element, kw, kh);
+  if (*mask == 0) return set_err(ctx, VF_E_INVALID, 0, "%s: an empty element (no member)", fn);
+  if (op == VF_RANK_MEDIAN) {
+    if (kw != kh || (kw != 3 && kw != 5))
+      return set_err(ctx, VF_E_INVALID, 0, "%s: median over a %d x %d element; the square has side 3 or 5", fn, kw, kh);
+    if (*mask != ((uint64_t)1 << (kw * kh)) - 1)
+      return set_err(ctx, VF_E_INVALID, 0, "%s: median takes the full square, every entry a member", fn);
+    if (border != VF_BORDER_REPLICATE)
+      return set_err(ctx, VF_E_INVALID, 0, "%s: median with border %d; cv2.medianBlur replicates (border %d)", fn, border,
+                     VF_BORDER_REPLICATE);
+  }
+  return VF_OK;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_rank_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels, int op,
+                             const uint8_t *element, int kw, int kh, int border, void *stream) {
+  VF_CHECK_CTX(ctx);
+  uint64_t mask = 0;
+  int rc = check_rank(ctx, "vf_rank_device", op, element, kw, kh, border, &mask);
+  if (rc != VF_OK) return rc;
+  if (channels != 1 && channels != 3)
+    return set_err(ctx, VF_E_INVALID, 0, "vf_rank_device: channels=%d, a frame has 1 or 3", channels);
+  if (width == 0 && height == 0) return VF_OK;  // the empty frame
+  if ((rc = check_frame_shape(ctx, "vf_rank_device", width, height, channels)) != VF_OK) return rc;
+  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "vf_rank_device: NULL buffer");
+  const size_t nbytes = (size_t)width * (size_t)channels * (size_t)height;
+  const uint8_t *s = (const uint8_t *)dsrc, *d = (const uint8_t *)ddst;
+  if (s < d + nbytes && d < s + nbytes)  // out of place only: a tap reads what a neighbour writes
+    return set_err(ctx, VF_E_INVALID, 0, "vf_rank_device: src and dst overlap");
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, vf::launch_rank(dsrc, ddst, width, channels, height, 0, height, 0, height, op, mask, kw, kh, border,
+                              (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_rank_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                  const int *heights, int n, int channels, int op, const uint8_t *element, int kw, int kh,
+                                  int border) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_rank_frames_host";
+  uint64_t mask = 0;
+  const int rc = check_rank(ctx, fn, op, element, kw, kh, border, &mask);
+  if (rc != VF_OK) return rc;
+  return neighbour_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, kh / 2,
+                               [&](const uint8_t *din, uint8_t *dout, int w, int h, const vf::conv::Band &b, hipStream_t st) {
+                                 return vf::launch_rank(din, dout, w, channels, h, b.y0, b.y1 - b.y0, b.s0, b.s1 - b.s0, op,
+                                                        mask, kw, kh, border, st);
+                               });
 }
 
 // ---- memory helpers ------------------------------------------------------------------------
@@ -927,7 +1010,7 @@ namespace {
 
 using vf::jpeg::Filter;
 
-// decode -> filter -> encode, for every vf_jpeg_{invert,lut,conv}
+// decode -> filter -> encode, for every vf_jpeg_{invert,lut,conv,rank}
 int jpeg_filter(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
                 int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes, const Filter &filt) {
   if (n < 0 || (n > 0 && (!jpegs || !jpeg_sizes || !outs || !caps || !sizes)))
@@ -976,7 +1059,7 @@ int jpeg_filter_bench(vf_ctx *ctx, const char *fn, const uint8_t *const *jpegs, 
   return jpeg_status(ctx, rc, std::string(fn) + ": " + err);
 }
 
-// The two builders of a batch's filter from an entry point's arguments, checked first (fn: its
+// The builders of a batch's filter from an entry point's arguments, checked first (fn: its
 // name, for the message).  The inversion is Filter{}.
 int table_filter(vf_ctx *ctx, const char *fn, const uint8_t *table, int channels, Filter *out) {
   const int rc = check_table(ctx, fn, table, channels);
@@ -994,6 +1077,15 @@ int conv_filter(vf_ctx *ctx, const char *fn, const int16_t *weights, int kw, int
   out->kind = Filter::kConv;
   out->conv = vf::jpeg::ConvSpec{{}, kw, kh, shift, border};
   std::memcpy(out->conv.w, weights, sizeof(int16_t) * (size_t)(kw * kh));
+  return VF_OK;
+}
+
+int rank_filter(vf_ctx *ctx, const char *fn, int op, const uint8_t *element, int kw, int kh, int border, Filter *out) {
+  uint64_t mask = 0;
+  const int rc = check_rank(ctx, fn, op, element, kw, kh, border, &mask);
+  if (rc != VF_OK) return rc;
+  out->kind = Filter::kRank;
+  out->rank = vf::jpeg::RankSpec{op, mask, kw, kh, border};
   return VF_OK;
 }
 
@@ -1120,5 +1212,33 @@ VF_EXPORT int vf_jpeg_bench_conv(vf_ctx *ctx, const uint8_t *const *jpegs, const
   Filter filter;
   if (const int rc = conv_filter(ctx, "vf_jpeg_bench_conv", weights, kw, kh, shift, border, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_conv", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
+                           stage_ms, filter);
+}
+
+VF_EXPORT int vf_jpeg_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int op,
+                           const uint8_t *element, int kw, int kh, int border, int quality, int subsamp, int flags,
+                           uint8_t *const *outs, const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = rank_filter(ctx, "vf_jpeg_rank", op, element, kw, kh, border, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_rank", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
+}
+
+VF_EXPORT int vf_jpeg_rank_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int op,
+                                  const uint8_t *element, int kw, int kh, int border, int quality, int subsamp,
+                                  int flags, uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = rank_filter(ctx, "vf_jpeg_rank_submit", op, element, kw, kh, border, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_rank_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
+}
+
+VF_EXPORT int vf_jpeg_bench_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int op,
+                                 const uint8_t *element, int kw, int kh, int border, int quality, int subsamp,
+                                 int flags, int iters, float *ms, float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = rank_filter(ctx, "vf_jpeg_bench_rank", op, element, kw, kh, border, &filter)) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_rank", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
                            stage_ms, filter);
 }

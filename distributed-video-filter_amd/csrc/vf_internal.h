@@ -52,6 +52,16 @@ hipError_t launch_conv(const void *dsrc, void *ddst, int width, int channels, in
 bool conv_narrow_fits(const int16_t *weights, int count);  // sum|K| * 255 < 2^15
 int conv_form_env();
 
+// The rank filters (vf_rank.hip): erode, dilate, median, out of place, with launch_conv's geometry
+// and row arguments (frame_h, output rows, source rows: bands work the same way).  op: a VF_RANK_*.
+// mask: bit j * kw + i set when (row j, column i) of the kw x kh element is a member (rank_mask
+// builds it from the element's bytes); at least one member.  The median takes the full 3 x 3 or
+// 5 x 5 square and the replicate border only.  border: a conv::k* of vf_conv_border.h; for erode
+// and dilate a tap outside the frame under kConstant is left out of the set.
+uint64_t rank_mask(const uint8_t *element, int kw, int kh);
+hipError_t launch_rank(const void *dsrc, void *ddst, int width, int channels, int frame_h, int y0, int nrows, int s0,
+                       int nsrc, int op, uint64_t mask, int kw, int kh, int border, hipStream_t stream);
+
 // Up to kMappedMax page-locked host ranges, by their device addresses, inverted in place over
 // PCIe by one launch (vf_kernels.hip invert_mapped_kernel; passed by value as kernel arguments).
 constexpr int kMappedMax = 64;

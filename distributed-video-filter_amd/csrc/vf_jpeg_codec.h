@@ -97,15 +97,25 @@ struct ConvSpec {
   int kw, kh, shift, border;
 };
 
+// The rank filter of a batch (vf_jpeg_rank*): `op` a VF_RANK_*, `mask` the members of the kw x kh
+// element (bit j * kw + i), `border` a VF_BORDER_* (DESIGN.md 18).
+struct RankSpec {
+  int op;
+  uint64_t mask;
+  int kw, kh, border;
+};
+
 // The filter of one batch of the invert path, as one value (vf_api.hip builds it from an entry point's
 // checked arguments); default-constructed, the inversion (cv2.bitwise_not).  The codec copies it, so
-// a batch resynchronised at wait_invert is filtered again by the same table or kernel.
+// a batch resynchronised at wait_invert is filtered again by the same table, kernel or element.
 struct Filter {
-  enum Kind { kNone, kInvert, kTable, kConv } kind = kInvert;  // kNone: the plain decode, pixels stay as decoded
+  enum Kind { kNone, kInvert, kTable, kConv, kRank } kind = kInvert;  // kNone: the plain decode, pixels stay as decoded
   LutTable lut = {};   // kTable: cv2.LUT on the decoded BGR pixels; a one-channel table is stored three times
   ConvSpec conv = {};  // kConv: cv2.filter2D on them
+  RankSpec rank = {};  // kRank: cv2.erode / dilate / medianBlur on them
   bool in_colour() const { return kind == kInvert || kind == kTable; }  // the colour stage filters
-  bool between() const { return kind == kConv; }  // a convolution runs between decode (d_pix_) and encode (d_pix2_)
+  // a neighbourhood filter runs between decode (d_pix_) and encode (d_pix2_)
+  bool between() const { return kind == kConv || kind == kRank; }
 };
 
 int header_info(const uint8_t *jpeg, size_t size, int *w, int *h, int *subsamp, int *colorspace, std::string *err);

@@ -872,18 +872,24 @@ int Codec::prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs
   return kOk;
 }
 
-// The invert path's tail behind the decode.  With a convolution the decode left plain BGR pixels
-// in d_pix_ (the plan is not fused); each frame goes through the raw kernel (vf_conv.hip) into
-// d_pix2_ at the same offset and the encoder reads that.  settle_decode's tails call this, so a
-// batch resynchronised at wait_invert is filtered again from freshly decoded pixels: once.
+// The invert path's tail behind the decode.  With a neighbourhood filter (a convolution or a rank
+// filter) the decode left plain BGR pixels in d_pix_ (the plan is not fused); each frame goes
+// through the raw kernel (vf_conv.hip, vf_rank.hip) into d_pix2_ at the same offset and the encoder
+// reads that.  settle_decode's tails call this, so a batch resynchronised at wait_invert is
+// filtered again from freshly decoded pixels: once.
 int Codec::run_filter_encode(bool fastdct, std::string *err) {
   if (!filter_.between()) return run_encode(1, fastdct, d_pix_.as<uint8_t>(), err);
   CK(d_pix2_.ensure(dpix_bytes_));
   const ConvSpec &k = filter_.conv;
+  const RankSpec &r = filter_.rank;
   for (int f = 0; f < dn_; ++f) {
     const DecFrame &F = dfr_[(size_t)f];
-    CK(launch_conv(d_pix_.as<uint8_t>() + F.out_off, d_pix2_.as<uint8_t>() + F.out_off, F.g.w, 3, F.g.h, 0, F.g.h, 0,
-                   F.g.h, k.w, k.kw, k.kh, k.shift, k.border, 0, s_));
+    const uint8_t *src = d_pix_.as<uint8_t>() + F.out_off;
+    uint8_t *dst = d_pix2_.as<uint8_t>() + F.out_off;
+    if (filter_.kind == Filter::kRank)
+      CK(launch_rank(src, dst, F.g.w, 3, F.g.h, 0, F.g.h, 0, F.g.h, r.op, r.mask, r.kw, r.kh, r.border, s_));
+    else
+      CK(launch_conv(src, dst, F.g.w, 3, F.g.h, 0, F.g.h, 0, F.g.h, k.w, k.kw, k.kh, k.shift, k.border, 0, s_));
   }
   return run_encode(1, fastdct, d_pix2_.as<uint8_t>(), err);
 }

@@ -7,20 +7,25 @@ distributor.py).
                ``filter2d`` (the ``cv2.filter2D`` drop-in: blur, sharpen, Sobel, ...) and
                ``filter2d_frames``
   tables       builders of the usual 256-entry tables (gamma, levels, threshold, posterize, ...)
+               ``erode``, ``dilate``, ``median_blur`` (the ``cv2.erode`` / ``cv2.dilate`` /
+               ``cv2.medianBlur`` drop-ins) and ``rank_frames``
   kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
+  elements     builders of the usual structuring elements (rect, cross)
   _lib         ctypes binding to libvfilter_hip.so (include/vfilter.h)
 
 The worker loop, the inverter plugin and the distributor live in ``worker``,
 ``inverter`` and ``distributor`` (imported on demand; they need no GPU to import).
 """
-from . import kernels, tables  # noqa: F401
+from . import elements, kernels, tables  # noqa: F401
 from ._lib import (ABI_VERSION, Context, VFilterError, device_count, get_context,  # noqa: F401
                    library_path, load_library)
-from .filters import (as_kernel, as_table, bitwise_not, filter2d, filter2d_frames, invert,  # noqa: F401
-                      invert_batch, invert_bytes, invert_frames, lut, lut_frames)
+from .filters import (Rank, as_element, as_kernel, as_table, bitwise_not, dilate, erode, filter2d,  # noqa: F401
+                      filter2d_frames, invert, invert_batch, invert_bytes, invert_frames, lut, lut_frames,
+                      median_blur, rank_frames)
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
     "load_library", "bitwise_not", "invert", "invert_batch", "invert_bytes", "invert_frames",
     "as_table", "lut", "lut_frames", "as_kernel", "filter2d", "filter2d_frames", "kernels", "tables",
+    "Rank", "as_element", "erode", "dilate", "median_blur", "rank_frames", "elements",
 ]

@@ -103,6 +103,18 @@ SIGNATURES = {
     "vf_jpeg_bench_conv": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           _c_float_p, _c_float_p]),
+    "vf_rank_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "vf_rank_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vf_jpeg_rank": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_rank_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_rank": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          _c_float_p, _c_float_p]),
 }
 
 
@@ -435,6 +447,34 @@ class Context:
         self._check(self._lib.vf_conv_device(self._ctx, dsrc, ddst, width, height, channels, w.ctypes.data, w.shape[1],
                                              w.shape[0], shift, border, stream or None))
 
+    # -- rank filters (cv2.erode, cv2.dilate, cv2.medianBlur): vf_rank_* ----------------------------
+    @staticmethod
+    def _element(element) -> np.ndarray:
+        """``element`` (``filters.as_element``'s result) as an array to point at."""
+        e = np.asarray(element)
+        if e.dtype != np.uint8 or e.ndim != 2 or not e.flags.c_contiguous:
+            raise ValueError("element must be a C-contiguous kh x kw uint8 array (see vfilter.as_element)")
+        return e
+
+    def rank_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                         channels: int, op: int, element, border: int = 2) -> None:
+        n = len(srcs)
+        if not (len(dsts) == n == len(widths) == len(heights)):
+            raise ValueError("srcs, dsts, widths and heights must have the same length")
+        e = self._element(element)
+        sa = (ctypes.c_void_p * n)(*[_addr(s) for s in srcs])
+        da = (ctypes.c_void_p * n)(*[_addr(d) for d in dsts])
+        wa = (ctypes.c_int * n)(*[int(v) for v in widths])
+        ha = (ctypes.c_int * n)(*[int(v) for v in heights])
+        self._check(self._lib.vf_rank_frames_host(self._ctx, sa, da, wa, ha, n, channels, op, e.ctypes.data, e.shape[1],
+                                                  e.shape[0], border))
+
+    def rank_device(self, dsrc: int, ddst: int, width: int, height: int, channels: int, op: int, element,
+                    border: int = 2, stream: int = 0) -> None:
+        e = self._element(element)
+        self._check(self._lib.vf_rank_device(self._ctx, dsrc, ddst, width, height, channels, op, e.ctypes.data,
+                                             e.shape[1], e.shape[0], border, stream or None))
+
     # -- host -> host, asynchronous (page-locked buffers) -----------------------------------
     def invert_frames_async(self, srcs: Sequence, dsts: Sequence, nbytes: Sequence[int]) -> int:
         """Enqueue a batch whose buffers are all page-locked; returns a ticket for ``wait``.
@@ -617,15 +657,20 @@ class Context:
         self._check(self._lib.vf_jpeg_decode(self._ctx, ja, js, n, pixel_format, flags, oa, ca))
         return outs
 
-    # The three JPEG filters differ in one C function each and in the arguments that stand between the
+    # The JPEG filters differ in one C function each and in the arguments that stand between the
     # batch and the quality, ``extra`` below: none (invert), ``table, channels`` (lut), ``weights, kw,
-    # kh, shift, border`` (conv).  The pointers keep their arrays alive (``data_as``).
+    # kh, shift, border`` (conv), ``op, element, kw, kh, border`` (rank).  The pointers keep their
+    # arrays alive (``data_as``).
     def _table_args(self, table, channels: int) -> tuple:
         return self._table(table, channels).ctypes.data_as(_vp), channels
 
     def _weights_args(self, weights, shift: int, border: int) -> tuple:
         w = self._weights(weights)
         return w.ctypes.data_as(_vp), w.shape[1], w.shape[0], shift, border
+
+    def _element_args(self, op: int, element, border: int) -> tuple:
+        e = self._element(element)
+        return op, e.ctypes.data_as(_vp), e.shape[1], e.shape[0], border
 
     def _jpeg_submit(self, name: str, fn, extra, jpegs, sizes, quality: int, subsamp: int, flags: int) -> int:
         """Every ``jpeg_*_submit*``: stage the batch through ``fn`` and note its frame count under the
@@ -825,6 +870,34 @@ class Context:
         """``jpeg_bench_invert`` with the convolution between the decode and the encode (its time is
         in the total, not in a stage: it runs between the colour and the fdct stage events)."""
         return self._jpeg_bench(self._lib.vf_jpeg_bench_conv, self._weights_args(weights, shift, border), "color",
+                                jpegs, quality, subsamp, flags, iters)
+
+    # -- JPEG with a rank filter in place of the inversion (vf_jpeg_rank*); tickets are invert tickets ----
+    def jpeg_rank(self, jpegs: Sequence, op: int, element, border: int, quality: int, subsamp: int,
+                  flags: int = 0) -> list:
+        """decode -> cv2.erode / dilate / medianBlur -> encode for every JPEG on the GPU; returns bytes."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_rank_submit(jpegs, op, element, border, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_rank_submit(self, jpegs: Sequence, op: int, element, border: int, quality: int, subsamp: int,
+                         flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the rank filter; collect with the ``jpeg_invert_result*`` methods."""
+        return self._jpeg_submit("jpeg_rank_submit", self._lib.vf_jpeg_rank_submit,
+                                 self._element_args(op, element, border), jpegs, None, quality, subsamp, flags)
+
+    def jpeg_rank_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, op: int, element, border: int,
+                               quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_rank_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        return self._jpeg_submit("jpeg_rank_submit_addrs", self._lib.vf_jpeg_rank_submit,
+                                 self._element_args(op, element, border), addrs, sizes, quality, subsamp, flags)
+
+    def jpeg_bench_rank(self, jpegs: Sequence, op: int, element, border: int, quality: int, subsamp: int,
+                        flags: int = 0, iters: int = 10):
+        """``jpeg_bench_invert`` with the rank filter between the decode and the encode (its time is
+        in the total, not in a stage, as ``jpeg_bench_conv``'s)."""
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_rank, self._element_args(op, element, border), "color",
                                 jpegs, quality, subsamp, flags, iters)
 
 

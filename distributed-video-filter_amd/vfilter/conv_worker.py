@@ -38,18 +38,17 @@ def _shape3(shape) -> tuple:
     return s
 
 
-class ConvWorker(FilterWorker):
-    def __init__(self, *args, kernel, border: str = "reflect101", shape=DEFAULT_SHAPE, **kw):
-        filt = Kernel(kernel, border)  # refuses a bad kernel or border before any GPU work
-        self.shape = _shape3(shape)
-        super().__init__(*args, filter=filt, **kw)
-        if self.verbose:
-            kh, kw = filt.weights.shape
-            print(f"filter2D worker: {kh} x {kw} kernel / 2^{filt.shift}, {border}")
+class ShapedFilterWorker(FilterWorker):
+    """A FilterWorker whose raw filter needs each frame's shape (ConvWorker, RankWorker): from the
+    batch's wire metadata, else from ``shape=``.  A subclass adds ``frames_host``."""
 
-    @property
-    def kernel(self):
-        return self.filter.weights, self.filter.shift
+    def __init__(self, *args, filter, shape=DEFAULT_SHAPE, **kw):
+        self.shape = _shape3(shape)
+        super().__init__(*args, filter=filter, **kw)
+
+    def frames_host(self, srcs, dsts, widths, heights, channels: int) -> None:
+        """The worker's filter on raw frames of the given sizes and one channel count."""
+        raise NotImplementedError
 
     def _frame_shape(self, nbytes: int, meta=None) -> tuple:
         shape = _shape3(meta.shape) if meta is not None and getattr(meta, "shape", None) else self.shape
@@ -62,8 +61,23 @@ class ConvWorker(FilterWorker):
         chans = {s[2] for s in shapes}
         if len(chans) != 1:
             raise ValueError("the frames of one batch have one channel count")
-        self.ctx.conv_frames_host(srcs, dsts, [s[1] for s in shapes], [s[0] for s in shapes], chans.pop(),
-                                  *self.filter.args)
+        self.frames_host(srcs, dsts, [s[1] for s in shapes], [s[0] for s in shapes], chans.pop())
+
+
+class ConvWorker(ShapedFilterWorker):
+    def __init__(self, *args, kernel, border: str = "reflect101", shape=DEFAULT_SHAPE, **kw):
+        filt = Kernel(kernel, border)  # refuses a bad kernel or border before any GPU work
+        super().__init__(*args, filter=filt, shape=shape, **kw)
+        if self.verbose:
+            kh, kw = filt.weights.shape
+            print(f"filter2D worker: {kh} x {kw} kernel / 2^{filt.shift}, {border}")
+
+    @property
+    def kernel(self):
+        return self.filter.weights, self.filter.shift
+
+    def frames_host(self, srcs, dsts, widths, heights, channels: int) -> None:
+        self.ctx.conv_frames_host(srcs, dsts, widths, heights, channels, *self.filter.args)
 
 
 def main(argv=None):

@@ -299,6 +299,156 @@ def filter2d_frames(frames: Sequence, kernel, outs: Optional[List] = None, borde
     return outs
 
 
+# -- rank filters: cv2.erode, cv2.dilate, cv2.medianBlur ------------------------------------------
+
+RANK_OPS = {"erode": 0, "dilate": 1, "median": 2}  # VF_RANK_* (include/vfilter.h)
+
+
+def as_element(element=None) -> np.ndarray:
+    """A structuring element in the library's form: a C-contiguous uint8 ``kh x kw`` array of 0 and 1.
+
+    ``element`` is a 2-D array of integers, booleans or integral floats whose non-zero entries are
+    the members; sides are odd and at most 7 and at least one entry is a member.  ``None`` is the
+    3 x 3 rectangle, as cv2's empty kernel is.  Anything else raises ``ValueError``.
+    ``vfilter.elements`` builds the usual ones."""
+    if element is None:
+        return np.ones((3, 3), np.uint8)
+    e = np.asarray(element)
+    if e.ndim != 2 or e.size == 0:
+        raise ValueError(f"a structuring element is a 2-D array, not shape {e.shape}")
+    kh, kw = e.shape
+    if kh % 2 == 0 or kw % 2 == 0 or kh > 7 or kw > 7:
+        raise ValueError(f"a {kh} x {kw} structuring element; sides must be odd and at most 7")
+    if e.dtype.kind == "f":
+        if not np.array_equal(e, np.rint(e)):
+            raise ValueError("a structuring element holds integers (non-zero: member)")
+    elif e.dtype.kind not in "iub":
+        raise ValueError(f"a structuring element of dtype {e.dtype}")
+    out = np.ascontiguousarray(e != 0, dtype=np.uint8)
+    if not out.any():
+        raise ValueError("a structuring element needs at least one member")
+    return out
+
+
+def _rank_border(name: str, border) -> int:
+    try:
+        return BORDERS[border]
+    except (KeyError, TypeError):
+        raise ValueError(f"{name}: border must be one of {sorted(BORDERS)}, not {border!r}") from None
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Rank:
+    """``cv2.erode``, ``cv2.dilate`` or ``cv2.medianBlur`` as a batch's filter; build one with
+    ``Rank.erode``, ``Rank.dilate`` or ``Rank.median``.  The element is copied."""
+    op: str
+    op_code: int
+    element: np.ndarray  # uint8 0/1 kh x kw, read-only
+    border: str
+    border_code: int
+    family = "rank"
+
+    def __init__(self, op: str, element=None, border: str = "constant"):
+        if op not in RANK_OPS:
+            raise ValueError(f"rank: op must be one of {sorted(RANK_OPS)}, not {op!r}")
+        e = as_element(element).copy()
+        if op == "median":
+            if e.shape not in ((3, 3), (5, 5)) or not e.all():
+                raise ValueError("median: the full 3 x 3 or 5 x 5 square only")
+            if border != "replicate":
+                raise ValueError("median: cv2.medianBlur replicates the border; there is no other")
+        e.flags.writeable = False
+        fields = {"op": op, "op_code": RANK_OPS[op], "element": e, "border": border,
+                  "border_code": _rank_border(op, border)}
+        for name, v in fields.items():
+            object.__setattr__(self, name, v)
+
+    @classmethod
+    def erode(cls, element=None, border: str = "constant") -> "Rank":
+        return cls("erode", element, border)
+
+    @classmethod
+    def dilate(cls, element=None, border: str = "constant") -> "Rank":
+        return cls("dilate", element, border)
+
+    @classmethod
+    def median(cls, ksize: int) -> "Rank":
+        if isinstance(ksize, bool) or not isinstance(ksize, (int, np.integer)) or ksize not in (3, 5):
+            raise ValueError(f"median_blur: ksize must be 3 or 5, not {ksize!r}")
+        return cls("median", np.ones((ksize, ksize), np.uint8), "replicate")
+
+    @property
+    def args(self) -> tuple:
+        return self.op_code, self.element, self.border_code
+
+
+def _rank_dst(name: str, src: np.ndarray, dst) -> np.ndarray:
+    if dst is None:
+        return np.empty_like(src)
+    if not isinstance(dst, np.ndarray) or dst.shape != src.shape or dst.dtype != src.dtype or not dst.flags.c_contiguous:
+        raise ValueError(f"{name}: dst must be C-contiguous with src's shape and dtype")
+    return dst
+
+
+def _rank_one(name: str, src, rank: Rank, dst, ctx) -> np.ndarray:
+    src = np.ascontiguousarray(_conv_frame(name, src))
+    dst = _rank_dst(name, src, dst)
+    channels = 1 if src.ndim == 2 else src.shape[2]
+    if src.size:
+        (ctx or get_context()).rank_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, *rank.args)
+    return dst
+
+
+def erode(src: np.ndarray, element=None, dst: Optional[np.ndarray] = None, border: str = "constant",
+          ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.erode(src, element)`` on uint8 ``H x W`` or ``H x W x 3`` input: per channel
+    the minimum over the element's members, anchor at the centre, one iteration.  ``element`` as for
+    ``as_element`` (``None``: the 3 x 3 rectangle).  ``border`` "constant", the default, is cv2's
+    default border: a tap outside the frame is left out of the minimum -- unlike ``filter2d``, where
+    the constant is 0; "reflect101" and "replicate" read the frame as ``filter2d`` does.  ``dst`` as
+    for ``filter2d``; it may not be ``src``."""
+    return _rank_one("erode", src, Rank.erode(element, border), dst, ctx)
+
+
+def dilate(src: np.ndarray, element=None, dst: Optional[np.ndarray] = None, border: str = "constant",
+           ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.dilate(src, element)``: ``erode`` with the maximum (the element is not
+    reflected, as in cv2).  ``border`` "constant", the default, leaves a tap outside the frame out of
+    the maximum -- unlike ``filter2d``, where the constant is 0 (for the maximum of uint8 the two
+    agree unless no tap of the element lands in the frame)."""
+    return _rank_one("dilate", src, Rank.dilate(element, border), dst, ctx)
+
+
+def median_blur(src: np.ndarray, ksize: int, dst: Optional[np.ndarray] = None,
+                ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.medianBlur(src, ksize)`` on uint8 ``H x W`` or ``H x W x 3`` input, ``ksize``
+    3 or 5: per channel the median of the ``ksize x ksize`` square, the border replicated (cv2 offers
+    no other).  ``dst`` as for ``filter2d``."""
+    return _rank_one("median_blur", src, Rank.median(ksize), dst, ctx)
+
+
+def rank_frames(frames: Sequence, rank: Rank, outs: Optional[List] = None, ctx: Optional[Context] = None) -> List:
+    """A ``Rank`` filter over separately stored frames of one channel count and mixed sizes in one
+    call.  Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
+    if not isinstance(rank, Rank):
+        raise ValueError("rank_frames: rank is a vfilter.Rank (Rank.erode, Rank.dilate, Rank.median)")
+    srcs = [np.ascontiguousarray(_conv_frame("rank_frames", f)) for f in frames]
+    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
+    if len(chans) > 1:
+        raise ValueError("rank_frames: the frames of one call have one channel count")
+    if outs is None:
+        outs = [np.empty_like(s) for s in srcs]
+    elif len(outs) != len(srcs) or any(o.shape != s.shape or o.dtype != np.uint8 or not o.flags.c_contiguous
+                                       for o, s in zip(outs, srcs)):
+        raise ValueError("rank_frames: outs must be C-contiguous uint8 arrays of the frames' shapes")
+    live = [(s, o) for s, o in zip(srcs, outs) if s.size]
+    if live:
+        (ctx or get_context()).rank_frames_host([s for s, _ in live], [o for _, o in live],
+                                                [s.shape[1] for s, _ in live], [s.shape[0] for s, _ in live],
+                                                chans.pop(), *rank.args)
+    return outs
+
+
 def invert_frames(frames: Sequence, outs: Optional[List] = None,
                   ctx: Optional[Context] = None) -> List:
     """Invert separately stored frames (ndarrays or bytes-likes; mixed sizes allowed) with

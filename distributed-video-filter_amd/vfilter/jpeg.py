@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import Invert, Kernel, Table
+from .filters import Invert, Kernel, Rank, Table
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -94,7 +94,7 @@ class TurboJPEG:
         return self.ctx.jpeg_encode(list(imgs), pixel_format, quality, jpeg_subsample,
                                     self._enc_flags(flags, quality))
 
-    # One filter value (``vfilter.filters``: Invert, Table, Kernel) between decode and encode.  The
+    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank) between decode and encode.  The
     # ``invert*``, ``lut*`` and ``filter2d*`` methods below are these three with their filter built
     # from the call's own arguments.
     def filter_batch(self, jpeg_bufs: Sequence, filt, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
@@ -174,6 +174,37 @@ class TurboJPEG:
     def filter2d_batch_submit_addrs(self, addrs, sizes, kernel, border: str = "reflect101", quality: int = 85,
                                     jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> int:
         return self.filter_batch_submit_addrs(addrs, sizes, Kernel(kernel, border), quality, jpeg_subsample, flags)
+
+    # -- rank filters: cv2.erode / cv2.dilate / cv2.medianBlur between decode and encode ---------------
+    # The submit forms go through ``filter_batch_submit*`` with a ``vfilter.filters.Rank``.
+    def erode(self, jpeg_buf, element=None, border: str = "constant", quality: int = 85,
+              jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(cv2.erode(decode(jpeg_buf), element))`` on the GPU, the pixels never leaving it.
+        ``element`` and ``border`` as for ``vfilter.erode``; each channel of the decoded BGR frame on
+        its own."""
+        return self.filter_batch([jpeg_buf], Rank.erode(element, border), quality, jpeg_subsample, flags)[0]
+
+    def erode_batch(self, jpeg_bufs: Sequence, element=None, border: str = "constant", quality: int = 85,
+                    jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, Rank.erode(element, border), quality, jpeg_subsample, flags)
+
+    def dilate(self, jpeg_buf, element=None, border: str = "constant", quality: int = 85,
+               jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(cv2.dilate(decode(jpeg_buf), element))`` on the GPU."""
+        return self.filter_batch([jpeg_buf], Rank.dilate(element, border), quality, jpeg_subsample, flags)[0]
+
+    def dilate_batch(self, jpeg_bufs: Sequence, element=None, border: str = "constant", quality: int = 85,
+                     jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, Rank.dilate(element, border), quality, jpeg_subsample, flags)
+
+    def median_blur(self, jpeg_buf, ksize: int, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                    flags: int = 0) -> bytes:
+        """``encode(cv2.medianBlur(decode(jpeg_buf), ksize))`` on the GPU; ``ksize`` 3 or 5."""
+        return self.filter_batch([jpeg_buf], Rank.median(ksize), quality, jpeg_subsample, flags)[0]
+
+    def median_blur_batch(self, jpeg_bufs: Sequence, ksize: int, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                          flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, Rank.median(ksize), quality, jpeg_subsample, flags)
 
     def invert_batch_result_into_addrs(self, ticket: int, out_addrs, cap: int):
         """(sizes, {i: JPEG that did not fit}): each result written at ``out_addrs[i]`` (``cap``

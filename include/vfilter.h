@@ -378,6 +378,54 @@ int vf_jpeg_bench_conv(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
                        const int16_t *weights, int kw, int kh, int shift, int border, int quality,
                        int subsamp, int flags, int iters, float *ms, float *stage_ms);
 
+/* ---- rank filters (cv2.erode, cv2.dilate, cv2.medianBlur) ----------------------------------
+ * For uint8 frames of 1 or 3 interleaved channels in packed rows, every channel on its own, exact
+ * (DESIGN.md 18).  `element` is a HOST pointer to kw * kh bytes, row-major (kh rows of kw), read
+ * during the call only; non-zero means "member".  kw and kh are odd and at most 7, at least one
+ * member; the anchor is the centre and offsets are not reflected.
+ *   VF_RANK_ERODE   the minimum over the members' taps, 255 when no tap resolves to a pixel
+ *   VF_RANK_DILATE  the maximum over them, 0 when none does
+ *   VF_RANK_MEDIAN  the median of the full square: kw == kh in {3, 5}, every entry non-zero, and
+ *                   `border` VF_BORDER_REPLICATE (cv2.medianBlur has no other)
+ * `border` is one of VF_BORDER_*.  For erode and dilate VF_BORDER_CONSTANT is cv2's default
+ * border: a tap outside the frame is left out of the set (NOT read as 0, unlike vf_conv_*).
+ * Anything else, a NULL `element`, `channels` other than 1 or 3, or a frame with width <= 0 or
+ * height <= 0 (other than the empty 0 x 0 frame, which is skipped) is VF_E_INVALID. */
+#define VF_RANK_ERODE  0
+#define VF_RANK_DILATE 1
+#define VF_RANK_MEDIAN 2
+
+/* Enqueue the filter on `stream` over device memory (width * height * channels bytes each).
+ * Returns after the launch (does not synchronise); any alignment.  Out of place only: ranges
+ * that overlap are VF_E_INVALID. */
+int vf_rank_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                   int op, const uint8_t *element, int kw, int kh, int border, void *stream);
+
+/* The filter on `n` separately allocated host frames (srcs[i] -> dsts[i], widths[i] x heights[i]
+ * x channels), synchronous, as vf_conv_frames_host: srcs[i] == dsts[i] is allowed; a frame larger
+ * than the context's staging is cut into bands of rows with their halo; VF_E_INVALID when kh rows
+ * of a frame do not fit it. */
+int vf_rank_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                        const int *widths, const int *heights, int n, int channels, int op,
+                        const uint8_t *element, int kw, int kh, int border);
+
+/* vf_jpeg_invert with the rank filter in place of the inversion: decode -> filter -> encode on
+ * the GPU, on each channel of the decoded BGR frame. */
+int vf_jpeg_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int op,
+                 const uint8_t *element, int kw, int kh, int border, int quality, int subsamp,
+                 int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the rank filter (element copied).  The ticket is an invert ticket:
+ * collect with vf_jpeg_invert_query / _wait / _fetch / _scatter. */
+int vf_jpeg_rank_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                        int op, const uint8_t *element, int kw, int kh, int border, int quality,
+                        int subsamp, int flags, uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the rank filter between the decode and the encode. */
+int vf_jpeg_bench_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                       int op, const uint8_t *element, int kw, int kh, int border, int quality,
+                       int subsamp, int flags, int iters, float *ms, float *stage_ms);
+
 #ifdef __cplusplus
 }
 #endif
