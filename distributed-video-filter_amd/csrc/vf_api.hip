@@ -23,6 +23,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -35,6 +36,7 @@
 #include "vf_lut_split.h"
 #include "vf_conv_bands.h"
 #include "vf_conv_border.h"
+#include "vf_chain_plan.h"
 
 #define VF_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -84,6 +86,9 @@ struct vf_ctx {
   size_t raw_cap = 0;
   hipStream_t raw_stream = nullptr;
   uint8_t *raw_din = nullptr, *raw_dout = nullptr;
+  // vf_chain_frames_host's intermediate values: device buffers sized like raw_din, allocated by the
+  // first program that needs them (raw_mu held), freed with the context
+  std::vector<uint8_t *> raw_scratch;
 };
 
 namespace {
@@ -263,6 +268,7 @@ VF_EXPORT int vf_destroy(vf_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->raw_stream);
     (void)hipFree(ctx->raw_din);
     (void)hipFree(ctx->raw_dout);
+    for (uint8_t *p : ctx->raw_scratch) (void)hipFree(p);
     (void)hipStreamDestroy(ctx->raw_stream);
   }
   for (vf::jpeg::Codec *c : ctx->jpeg_all) delete c;  // each synchronises its stream first
@@ -679,6 +685,131 @@ VF_EXPORT int vf_rank_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
                                });
 }
 
+// ---- filter chains: a program of table / conv / rank / binary steps on raw frames ------------------
+
+namespace {
+
+// A vf_step list as a validated, folded program: every step through its single-filter check, then
+// the structure (vf_chain_plan.h).  masks[i]: the element of step i + 1 of the FOLDED program.
+int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps, int channels, vf::chain::Program *out,
+                  std::vector<uint64_t> *masks) {
+  if (channels != 1 && channels != 3)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: channels=%d, a frame has 1 or 3", fn, channels);
+  if (nsteps < 1 || nsteps > VF_CHAIN_MAX_STEPS)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: a program of %d steps; it has 1 to %d", fn, nsteps, VF_CHAIN_MAX_STEPS);
+  if (!steps) return set_err(ctx, VF_E_INVALID, 0, "%s: steps is NULL", fn);
+  vf::chain::Program p;
+  int rc;
+  for (int i = 0; i < nsteps; ++i) {
+    const vf_step &in = steps[i];
+    vf::chain::Step s;
+    s.kind = in.kind;
+    s.a = in.a;
+    s.b = in.b;
+    s.op = in.op;
+    char at[96];
+    std::snprintf(at, sizeof at, "%s: step %d", fn, i + 1);
+    if (in.kind == VF_STEP_TABLE) {
+      if ((rc = check_table(ctx, at, static_cast<const uint8_t *>(in.data), in.channels)) != VF_OK) return rc;
+      s.channels = in.channels;
+      const uint8_t *t = static_cast<const uint8_t *>(in.data);
+      s.table.assign(t, t + 256 * (size_t)in.channels);
+    } else if (in.kind == VF_STEP_CONV) {
+      const int16_t *w = static_cast<const int16_t *>(in.data);
+      if ((rc = check_kernel(ctx, at, w, in.kw, in.kh, in.shift, in.border)) != VF_OK) return rc;
+      s.kw = in.kw, s.kh = in.kh, s.shift = in.shift, s.border = in.border;
+      s.weights.assign(w, w + (size_t)in.kw * in.kh);
+    } else if (in.kind == VF_STEP_RANK) {
+      const uint8_t *e = static_cast<const uint8_t *>(in.data);
+      uint64_t mask = 0;
+      if ((rc = check_rank(ctx, at, in.op, e, in.kw, in.kh, in.border, &mask)) != VF_OK) return rc;
+      s.kw = in.kw, s.kh = in.kh, s.border = in.border;
+      s.element.assign(e, e + (size_t)in.kw * in.kh);
+    } else if (in.kind != VF_STEP_BINARY) {
+      return set_err(ctx, VF_E_INVALID, 0, "%s: unknown kind %d", at, in.kind);
+    }
+    p.steps.push_back(std::move(s));
+  }
+  std::string why;
+  if (!vf::chain::validate(p, channels, &why)) return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  *out = vf::chain::fold(p);
+  masks->assign(out->steps.size(), 0);
+  for (size_t i = 0; i < out->steps.size(); ++i) {
+    const vf::chain::Step &s = out->steps[i];
+    if (s.kind == vf::chain::kRank) (*masks)[i] = vf::rank_mask(s.element.data(), s.kw, s.kh);
+  }
+  return VF_OK;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_binary_device(vf_ctx *ctx, const void *da, const void *db, void *ddst, size_t nbytes, int op,
+                               void *stream) {
+  VF_CHECK_CTX(ctx);
+  if (op < VF_BIN_SUBTRACT || op > VF_BIN_MAX) return set_err(ctx, VF_E_INVALID, 0, "vf_binary_device: unknown op %d", op);
+  if (nbytes == 0) return VF_OK;
+  if (!da || !db || !ddst) return set_err(ctx, VF_E_INVALID, 0, "vf_binary_device: NULL buffer");
+  if (overlaps_partially((const uint8_t *)da, (const uint8_t *)ddst, nbytes) ||
+      overlaps_partially((const uint8_t *)db, (const uint8_t *)ddst, nbytes))
+    return set_err(ctx, VF_E_INVALID, 0, "vf_binary_device: dst partially overlaps an operand");
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, vf::launch_binary(da, db, ddst, nbytes, op, ctx->cfg, (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_chain_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                   const int *heights, int n, int channels, const vf_step *steps, int nsteps) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_chain_frames_host";
+  vf::chain::Program prog;
+  std::vector<uint64_t> masks;
+  const int rc = chain_program(ctx, fn, steps, nsteps, channels, &prog, &masks);
+  if (rc != VF_OK) return rc;
+  const vf::chain::Buffers bufs = vf::chain::assign_buffers(prog);
+  const int form = vf::conv_form_env();
+  const int nst = prog.size();
+  // One band: value v's row y sits at (its buffer) + (y - band.s0) * row, every buffer at the one
+  // row origin, so an in-place step is dst == operand exactly.  Buffer 0 is the band's upload, the
+  // others are the context's scratch (the pieces of one fill share it: they run in order on the
+  // one stream); the last step writes the band's output rows straight into dout.
+  return neighbour_frames_host(
+      ctx, fn, srcs, dsts, widths, heights, n, channels, vf::chain::reach(prog),
+      [&](uint8_t *din, uint8_t *dout, int w, int h, const vf::conv::Band &b, hipStream_t st) -> hipError_t {
+        const size_t alloc = ((ctx->raw_cap + 15 + 15) & ~(size_t)15);
+        while ((int)ctx->raw_scratch.size() + 1 < bufs.count) {
+          void *p = nullptr;
+          const hipError_t e = hipMalloc(&p, alloc);
+          if (e != hipSuccess) return e;
+          ctx->raw_scratch.push_back(static_cast<uint8_t *>(p));
+        }
+        const size_t row = (size_t)w * (size_t)channels;
+        const std::vector<vf::chain::Rows> need = vf::chain::rows_needed(prog, h, b.y0, b.y1);
+        auto at = [&](int v, int y) -> uint8_t * {
+          uint8_t *base = bufs.of[v] == 0 ? din : ctx->raw_scratch[bufs.of[v] - 1];
+          return base + (size_t)(y - b.s0) * row;
+        };
+        for (int i = 1; i <= nst; ++i) {
+          const vf::chain::Step &s = prog.steps[i - 1];
+          const vf::chain::Rows r = need[i], ra = need[s.a];
+          uint8_t *dst = i == nst ? dout : at(i, r.lo);
+          const size_t nbytes = (size_t)(r.hi - r.lo) * row;
+          hipError_t e;
+          if (s.kind == vf::chain::kTable)
+            e = vf::launch_lut(at(s.a, r.lo), dst, nbytes, s.table.data(), s.channels, 0, ctx->cfg, st);
+          else if (s.kind == vf::chain::kBinary)
+            e = vf::launch_binary(at(s.a, r.lo), at(s.b, r.lo), dst, nbytes, s.op, ctx->cfg, st);
+          else if (s.kind == vf::chain::kConv)
+            e = vf::launch_conv(at(s.a, ra.lo), dst, w, channels, h, r.lo, r.hi - r.lo, ra.lo, ra.hi - ra.lo,
+                                s.weights.data(), s.kw, s.kh, s.shift, s.border, form, st);
+          else
+            e = vf::launch_rank(at(s.a, ra.lo), dst, w, channels, h, r.lo, r.hi - r.lo, ra.lo, ra.hi - ra.lo, s.op,
+                                masks[i - 1], s.kw, s.kh, s.border, st);
+          if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+      });
+}
+
 // ---- memory helpers ------------------------------------------------------------------------
 
 VF_EXPORT int vf_alloc_device(vf_ctx *ctx, size_t nbytes, void **out) {
@@ -1089,6 +1220,26 @@ int rank_filter(vf_ctx *ctx, const char *fn, int op, const uint8_t *element, int
   return VF_OK;
 }
 
+// A program as a batch's filter.  One that folds to a single table, convolution or rank step runs
+// as that kind (a table in the fused colour stage); anything else is Filter::kChain, its plan
+// built here once and shared by the codec's copy.  The decoded frames have three channels.
+int chain_filter(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps, Filter *out) {
+  auto spec = std::make_shared<vf::jpeg::ChainSpec>();
+  const int rc = chain_program(ctx, fn, steps, nsteps, 3, &spec->prog, &spec->masks);
+  if (rc != VF_OK) return rc;
+  const int one = vf::chain::single_kind(spec->prog);
+  if (one >= 0) {
+    const vf::chain::Step &s = spec->prog.steps[0];
+    if (one == vf::chain::kTable) return table_filter(ctx, fn, s.table.data(), s.channels, out);
+    if (one == vf::chain::kConv) return conv_filter(ctx, fn, s.weights.data(), s.kw, s.kh, s.shift, s.border, out);
+    return rank_filter(ctx, fn, s.op, s.element.data(), s.kw, s.kh, s.border, out);
+  }
+  spec->bufs = vf::chain::assign_buffers(spec->prog);
+  out->kind = Filter::kChain;
+  out->chain = std::move(spec);
+  return VF_OK;
+}
+
 }  // namespace
 
 VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
@@ -1240,5 +1391,35 @@ VF_EXPORT int vf_jpeg_bench_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const
   Filter filter;
   if (const int rc = rank_filter(ctx, "vf_jpeg_bench_rank", op, element, kw, kh, border, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_rank", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
+                           stage_ms, filter);
+}
+
+// ---- JPEG with a filter chain in place of the inversion ---------------------------------------------
+
+VF_EXPORT int vf_jpeg_chain(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                            const vf_step *steps, int nsteps, int quality, int subsamp, int flags, uint8_t *const *outs,
+                            const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = chain_filter(ctx, "vf_jpeg_chain", steps, nsteps, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_chain", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
+}
+
+VF_EXPORT int vf_jpeg_chain_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                   const vf_step *steps, int nsteps, int quality, int subsamp, int flags,
+                                   uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = chain_filter(ctx, "vf_jpeg_chain_submit", steps, nsteps, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_chain_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
+}
+
+VF_EXPORT int vf_jpeg_bench_chain(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                  const vf_step *steps, int nsteps, int quality, int subsamp, int flags, int iters,
+                                  float *ms, float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = chain_filter(ctx, "vf_jpeg_bench_chain", steps, nsteps, &filter)) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_chain", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
                            stage_ms, filter);
 }

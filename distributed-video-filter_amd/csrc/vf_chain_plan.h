@@ -1,0 +1,246 @@
+// vf_chain_plan.h — the plan of a filter chain (host only, no HIP, so
+// tests/chain/chain_plan_check.cc checks it on the CPU).  Not installed.
+//
+// A program is a straight-line list of 1 .. kMaxSteps steps over values: value 0 is the input
+// frame, value i the result of step i (1-based), the program's result the last step's value.  A
+// step names its operand a, a binary step b as well; operands are earlier values.  From a
+// validated program this file derives
+//   * folding   a table step whose only reader is a table step is composed into that reader;
+//   * buffers   which buffer each value lives in, assigned by last use;
+//   * rows      working backwards from an output band, the rows of every value that must exist,
+//               and the program's total vertical reach R.
+// Every step sees whole-frame borders: a step that makes rows [lo, hi) of its value from an
+// operand of vertical radius r reads the operand's rows [lo - r, hi + r) clipped to the frame, and
+// resolves its border in FRAME coordinates (vf_conv_border.h) exactly as one band of
+// vf_conv_bands.h does.  So the result is what running the steps one after the other on whole
+// frames gives, however the frame is cut into bands.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+namespace vf {
+namespace chain {
+
+constexpr int kMaxSteps = 8;  // VF_CHAIN_MAX_STEPS (include/vfilter.h)
+constexpr int kMaxSide = 7;   // the largest kernel or element side (conv::kMaxK)
+
+enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3 };                   // VF_STEP_*
+enum : int { kSubtract = 0, kAdd = 1, kAbsdiff = 2, kMin = 3, kMax = 4 };        // VF_BIN_*
+
+struct Step {
+  int kind = kTable;
+  int a = 0, b = 0;  // operand values; b is read by a binary step only
+  int op = 0;        // kRank: a VF_RANK_*; kBinary: a VF_BIN_*
+  int kw = 0, kh = 0, shift = 0, border = 0;  // kConv, kRank
+  int channels = 1;                           // kTable: 1 or 3
+  std::vector<uint8_t> table;    // kTable: channels x 256, planar
+  std::vector<int16_t> weights;  // kConv: kw * kh
+  std::vector<uint8_t> element;  // kRank: kw * kh
+};
+
+struct Program {
+  std::vector<Step> steps;  // steps[i - 1] makes value i
+  int size() const { return (int)steps.size(); }
+};
+
+inline bool is_neighbourhood(const Step &s) { return s.kind == kConv || s.kind == kRank; }
+inline int radius(const Step &s) { return is_neighbourhood(s) ? s.kh / 2 : 0; }  // vertical
+
+// Is value v read by step s?
+inline bool reads(const Step &s, int v) { return s.a == v || (s.kind == kBinary && s.b == v); }
+
+// The structure of a program for frames of `frame_channels` channels.  false with the reason in
+// *why.  The contents of a table, a kernel or an element are the single-filter checks' business.
+inline bool validate(const Program &p, int frame_channels, std::string *why) {
+  const int n = p.size();
+  auto fail = [&](const std::string &m) {
+    if (why) *why = m;
+    return false;
+  };
+  if (n < 1) return fail("an empty program");
+  if (n > kMaxSteps)
+    return fail("a program of " + std::to_string(n) + " steps; at most " + std::to_string(kMaxSteps));
+  if (frame_channels != 1 && frame_channels != 3) return fail("frames have 1 or 3 channels");
+  for (int i = 1; i <= n; ++i) {
+    const Step &s = p.steps[i - 1];
+    const std::string at = "step " + std::to_string(i) + ": ";
+    if (s.kind < kTable || s.kind > kBinary) return fail(at + "unknown kind " + std::to_string(s.kind));
+    if (s.a < 0 || s.a >= i)
+      return fail(at + "operand a = " + std::to_string(s.a) + " is not an earlier value");
+    if (s.kind == kBinary) {
+      if (s.b < 0 || s.b >= i)
+        return fail(at + "operand b = " + std::to_string(s.b) + " is not an earlier value");
+      if (s.op < kSubtract || s.op > kMax) return fail(at + "unknown binary op " + std::to_string(s.op));
+    }
+    if (s.kind == kTable) {
+      if (s.channels != 1 && s.channels != 3) return fail(at + "a table has 1 or 3 channels");
+      if (s.table.size() != (size_t)s.channels * 256) return fail(at + "a table holds channels x 256 bytes");
+      if (s.channels == 3 && frame_channels != 3) return fail(at + "a 3-channel table on 1-channel frames");
+    }
+    if (is_neighbourhood(s)) {
+      if (s.kw < 1 || s.kh < 1 || s.kw > kMaxSide || s.kh > kMaxSide || !(s.kw & 1) || !(s.kh & 1))
+        return fail(at + "sides are odd and at most " + std::to_string(kMaxSide));
+      const size_t count = (size_t)s.kw * (size_t)s.kh;
+      if (s.kind == kConv ? s.weights.size() != count : s.element.size() != count)
+        return fail(at + "the kernel or element does not hold kw x kh entries");
+    }
+  }
+  for (int v = 0; v < n; ++v) {  // every value but the last is read
+    bool read = false;
+    for (int i = v + 1; i <= n && !read; ++i) read = reads(p.steps[i - 1], v);
+    if (!read) return fail("value " + std::to_string(v) + " is read by no step (a dead value)");
+  }
+  return true;
+}
+
+// ---- folding -------------------------------------------------------------------------------------
+
+// then(first(v)) per channel: channels = 3 when either has 3.
+inline void compose_tables(const Step &first, const Step &then, Step *out) {
+  const int ch = first.channels == 3 || then.channels == 3 ? 3 : 1;
+  std::vector<uint8_t> t((size_t)ch * 256);
+  for (int c = 0; c < ch; ++c) {
+    const uint8_t *f = first.table.data() + (first.channels == 3 ? 256 * c : 0);
+    const uint8_t *g = then.table.data() + (then.channels == 3 ? 256 * c : 0);
+    for (int v = 0; v < 256; ++v) t[(size_t)c * 256 + v] = g[f[v]];
+  }
+  out->channels = ch;
+  out->table = std::move(t);
+}
+
+// The program with every table step whose only reader is a table step composed into that reader
+// (exact: both are per-byte maps).  The result computes the same picture in fewer steps.
+inline Program fold(const Program &in) {
+  Program p = in;
+  for (bool again = true; again;) {
+    again = false;
+    const int n = p.size();
+    for (int i = 1; i < n && !again; ++i) {
+      if (p.steps[i - 1].kind != kTable) continue;
+      int readers = 0, reader = 0;
+      for (int j = i + 1; j <= n; ++j)
+        if (reads(p.steps[j - 1], i)) ++readers, reader = j;
+      if (readers != 1 || p.steps[reader - 1].kind != kTable) continue;
+      Step &r = p.steps[reader - 1];
+      compose_tables(p.steps[i - 1], r, &r);
+      r.a = p.steps[i - 1].a;
+      p.steps.erase(p.steps.begin() + (i - 1));
+      for (Step &s : p.steps) {  // values above i move down by one
+        if (s.a > i) --s.a;
+        if (s.b > i) --s.b;
+      }
+      again = true;
+    }
+  }
+  return p;
+}
+
+// The kind a (folded) program may run as when it is one step on value 0 that is not binary, else
+// -1: a program that folds to one table step takes the JPEG path's fused colour stage.
+inline int single_kind(const Program &p) {
+  if (p.size() != 1 || p.steps[0].kind == kBinary || p.steps[0].a != 0) return -1;
+  return p.steps[0].kind;
+}
+
+// ---- buffers -------------------------------------------------------------------------------------
+
+struct Buffers {
+  std::vector<int> of;  // of[v]: the buffer of value v; of[0] == 0
+  int count = 0;        // buffers used
+  int result = 0;       // the buffer of the program's result
+};
+
+// Buffers by last use.  Buffer 0 holds value 0 and is reused once value 0 is dead.  A
+// neighbourhood step never writes the buffer it reads; a table or binary step writes in place over
+// an operand that dies at that step.  Every value of a buffer sits at one row origin (the band's
+// first source row), so "in place" is dst == operand exactly.
+inline Buffers assign_buffers(const Program &p) {
+  const int n = p.size();
+  std::vector<int> last(n + 1, 0);  // the last step that reads value v; the result outlives all
+  for (int i = 1; i <= n; ++i) {
+    last[p.steps[i - 1].a] = i;
+    if (p.steps[i - 1].kind == kBinary) last[p.steps[i - 1].b] = i;
+  }
+  last[n] = n + 1;
+  Buffers out;
+  out.of.assign(n + 1, 0);
+  std::vector<int> holder_dies{last[0]};  // per buffer: the last read of the value it holds
+  for (int i = 1; i <= n; ++i) {
+    const Step &s = p.steps[i - 1];
+    int pick = -1;
+    if (!is_neighbourhood(s)) {  // in place over an operand that dies here
+      if (last[s.a] == i) pick = out.of[s.a];
+      else if (s.kind == kBinary && last[s.b] == i) pick = out.of[s.b];
+    }
+    for (int k = 0; pick < 0 && k < (int)holder_dies.size(); ++k)
+      if (holder_dies[k] < i) pick = k;  // its value is dead: no step from i on reads it
+    if (pick < 0) {
+      pick = (int)holder_dies.size();
+      holder_dies.push_back(0);
+    }
+    out.of[i] = pick;
+    holder_dies[pick] = last[i];
+  }
+  out.count = (int)holder_dies.size();
+  out.result = out.of[n];
+  return out;
+}
+
+// ---- reach and row ranges ------------------------------------------------------------------------
+
+struct Rows {
+  int lo = 0, hi = 0;  // rows [lo, hi)
+};
+
+// The rows of every value that must exist for rows [y0, y1) of the result of a frame of H rows
+// (0 <= y0 < y1 <= H): out[v] for v = 0 .. n.  out[0] is the upload.
+inline std::vector<Rows> rows_needed(const Program &p, int H, int y0, int y1) {
+  const int n = p.size();
+  std::vector<Rows> need(n + 1);
+  std::vector<bool> have(n + 1, false);
+  need[n].lo = y0;
+  need[n].hi = y1;
+  have[n] = true;
+  auto want = [&](int v, int lo, int hi) {
+    if (lo < 0) lo = 0;
+    if (hi > H) hi = H;
+    if (!have[v]) {
+      need[v].lo = lo;
+      need[v].hi = hi;
+      have[v] = true;
+    } else {  // every range holds [y0, y1), so a union of ranges is a range
+      if (lo < need[v].lo) need[v].lo = lo;
+      if (hi > need[v].hi) need[v].hi = hi;
+    }
+  };
+  for (int i = n; i >= 1; --i) {
+    const Step &s = p.steps[i - 1];
+    if (!have[i]) continue;  // a dead value: validate() refuses those
+    const int r = radius(s);
+    want(s.a, need[i].lo - r, need[i].hi + r);
+    if (s.kind == kBinary) want(s.b, need[i].lo - r, need[i].hi + r);
+  }
+  return need;
+}
+
+// The program's total vertical reach: the largest summed radius along a path from the result to
+// value 0.  Rows [y0, y1) of the result read rows [y0 - R, y1 + R) of the input at the most.
+inline int reach(const Program &p) {
+  const int n = p.size();
+  std::vector<int> r(n + 1, -1);
+  r[n] = 0;
+  for (int i = n; i >= 1; --i) {
+    if (r[i] < 0) continue;
+    const Step &s = p.steps[i - 1];
+    const int t = r[i] + radius(s);
+    if (t > r[s.a]) r[s.a] = t;
+    if (s.kind == kBinary && t > r[s.b]) r[s.b] = t;
+  }
+  return r[0] < 0 ? 0 : r[0];
+}
+
+}  // namespace chain
+}  // namespace vf

@@ -62,6 +62,12 @@ uint64_t rank_mask(const uint8_t *element, int kw, int kh);
 hipError_t launch_rank(const void *dsrc, void *ddst, int width, int channels, int frame_h, int y0, int nrows, int s0,
                        int nsrc, int op, uint64_t mask, int kw, int kh, int border, hipStream_t stream);
 
+// ddst[i] = op(da[i], db[i]) over nbytes (vf_binary.hip), op a VF_BIN_*: the two-input step of a
+// filter chain.  Each pointer at any alignment; ddst == da or ddst == db exactly is allowed, a
+// partial overlap is not (the caller checks).  No device allocation; asynchronous on `stream`.
+hipError_t launch_binary(const void *da, const void *db, void *ddst, size_t nbytes, int op, const LaunchCfg &cfg,
+                         hipStream_t stream);
+
 // Up to kMappedMax page-locked host ranges, by their device addresses, inverted in place over
 // PCIe by one launch (vf_kernels.hip invert_mapped_kernel; passed by value as kernel arguments).
 constexpr int kMappedMax = 64;

@@ -6,11 +6,13 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "vf_chain_plan.h"
 #include "vf_jpeg.h"
 #include "vf_jpeg_plan.h"
 
@@ -105,17 +107,28 @@ struct RankSpec {
   int kw, kh, border;
 };
 
+// The filter chain of a batch (vf_jpeg_chain*): the validated, folded program (vf_chain_plan.h), the
+// element masks of its rank steps and its buffer assignment.  Immutable once built; a
+// Filter shares it, so a Filter of the other kinds grows by one pointer and not by the program.
+struct ChainSpec {
+  chain::Program prog;
+  std::vector<uint64_t> masks;  // masks[i]: step i + 1's element when it is a rank step
+  chain::Buffers bufs;
+};
+
 // The filter of one batch of the invert path, as one value (vf_api.hip builds it from an entry point's
 // checked arguments); default-constructed, the inversion (cv2.bitwise_not).  The codec copies it, so
 // a batch resynchronised at wait_invert is filtered again by the same table, kernel or element.
 struct Filter {
-  enum Kind { kNone, kInvert, kTable, kConv, kRank } kind = kInvert;  // kNone: the plain decode, pixels stay as decoded
+  enum Kind { kNone, kInvert, kTable, kConv, kRank, kChain } kind = kInvert;  // kNone: the plain decode, pixels stay as decoded
   LutTable lut = {};   // kTable: cv2.LUT on the decoded BGR pixels; a one-channel table is stored three times
   ConvSpec conv = {};  // kConv: cv2.filter2D on them
   RankSpec rank = {};  // kRank: cv2.erode / dilate / medianBlur on them
+  std::shared_ptr<const ChainSpec> chain;  // kChain: a program of those and the binary kernel, on them
   bool in_colour() const { return kind == kInvert || kind == kTable; }  // the colour stage filters
-  // a neighbourhood filter runs between decode (d_pix_) and encode (d_pix2_)
-  bool between() const { return kind == kConv || kind == kRank; }
+  // a neighbourhood filter or a chain runs between decode (d_pix_) and encode (d_pix2_, or the
+  // buffer that holds a chain's result)
+  bool between() const { return kind == kConv || kind == kRank || kind == kChain; }
 };
 
 int header_info(const uint8_t *jpeg, size_t size, int *w, int *h, int *subsamp, int *colorspace, std::string *err);
@@ -219,6 +232,7 @@ class Codec {
   DevBuf d_eplanes_;  // the invert path's encoder sample planes (plan_.fuse)
   Filter filter_;  // the batch's filter, set by the entry call before prepare_decode; the stages read it
   DevBuf d_pix2_;  // the convolution's output: the batch's frames at their d_pix_ offsets
+  std::vector<std::unique_ptr<DevBuf>> d_chain_;  // a chain's buffers 2, 3, ...: as d_pix2_ (0 is d_pix_, 1 d_pix2_)
   int dcm_ = -1;  // k_color layout shared by the batch's frames (1..3, 0 general), -1 mixed
   DevBuf d_efr_, d_etab_, d_hdr_, d_esegs_, d_etsum_, d_etotals_, d_dcq_, d_acbits_, d_acscr_, d_bits_, d_pre_, d_bitoff_, d_stream_, d_ffcnt_,
       d_outsize_, d_pack_;

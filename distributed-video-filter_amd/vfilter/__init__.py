@@ -9,6 +9,8 @@ distributor.py).
   tables       builders of the usual 256-entry tables (gamma, levels, threshold, posterize, ...)
                ``erode``, ``dilate``, ``median_blur`` (the ``cv2.erode`` / ``cv2.dilate`` /
                ``cv2.medianBlur`` drop-ins) and ``rank_frames``
+               ``Chain`` / ``Combine`` / ``Morph`` (a program of the filters above in one GPU pass),
+               ``chain``, ``chain_frames`` and ``morphology_ex`` (the ``cv2.morphologyEx`` drop-in)
   kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
   elements     builders of the usual structuring elements (rect, cross)
   _lib         ctypes binding to libvfilter_hip.so (include/vfilter.h)
@@ -19,13 +21,14 @@ The worker loop, the inverter plugin and the distributor live in ``worker``,
 from . import elements, kernels, tables  # noqa: F401
 from ._lib import (ABI_VERSION, Context, VFilterError, device_count, get_context,  # noqa: F401
                    library_path, load_library)
-from .filters import (Rank, as_element, as_kernel, as_table, bitwise_not, dilate, erode, filter2d,  # noqa: F401
-                      filter2d_frames, invert, invert_batch, invert_bytes, invert_frames, lut, lut_frames,
-                      median_blur, rank_frames)
+from .filters import (Chain, Combine, Morph, Rank, as_element, as_kernel, as_table, bitwise_not, chain,  # noqa: F401
+                      chain_frames, dilate, erode, filter2d, filter2d_frames, invert, invert_batch, invert_bytes,
+                      invert_frames, lut, lut_frames, median_blur, morphology_ex, rank_frames)
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
     "load_library", "bitwise_not", "invert", "invert_batch", "invert_bytes", "invert_frames",
     "as_table", "lut", "lut_frames", "as_kernel", "filter2d", "filter2d_frames", "kernels", "tables",
     "Rank", "as_element", "erode", "dilate", "median_blur", "rank_frames", "elements",
+    "Chain", "Combine", "Morph", "chain", "chain_frames", "morphology_ex",
 ]

@@ -115,7 +115,25 @@ SIGNATURES = {
     "vf_jpeg_bench_rank": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           _c_float_p, _c_float_p]),
+    "vf_binary_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
+    "vf_chain_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
+    "vf_jpeg_chain": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_chain_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_chain": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
 }
+
+STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
+CHAIN_MAX_STEPS = 8                                         # VF_CHAIN_MAX_STEPS
+
+
+class Step(ctypes.Structure):
+    """``vf_step`` of include/vfilter.h: one step of a filter chain's program."""
+    _fields_ = [("kind", ctypes.c_int), ("a", ctypes.c_int), ("b", ctypes.c_int), ("op", ctypes.c_int),
+                ("data", ctypes.c_void_p), ("kw", ctypes.c_int), ("kh", ctypes.c_int), ("shift", ctypes.c_int),
+                ("border", ctypes.c_int), ("channels", ctypes.c_int)]
 
 
 class VFilterError(RuntimeError):
@@ -474,6 +492,49 @@ class Context:
         e = self._element(element)
         self._check(self._lib.vf_rank_device(self._ctx, dsrc, ddst, width, height, channels, op, e.ctypes.data,
                                              e.shape[1], e.shape[0], border, stream or None))
+
+    # -- filter chains (vf_chain_*, vf_binary_device) ------------------------------------------------
+    def _steps(self, steps: Sequence):
+        """``steps`` -- ``filters.Chain.args[0]``: tuples ``(kind, a, b, op, data, shift, border)`` with
+        ``data`` the planar table bytes, the int16 weights, the element or ``None`` -- as a ``vf_step``
+        array, with the arrays it points at (keep both alive across the call)."""
+        arr = (Step * max(len(steps), 1))()
+        keep = []
+        for st, (kind, a, b, op, data, shift, border) in zip(arr, steps):
+            st.kind, st.a, st.b, st.op, st.shift, st.border = kind, a, b, op, shift, border
+            if kind == STEP_TABLE:
+                st.channels = len(data) // 256
+                d = self._table(data, st.channels)
+            elif kind == STEP_CONV:
+                d = self._weights(data)
+                st.kh, st.kw = d.shape
+            elif kind == STEP_RANK:
+                d = self._element(data)
+                st.kh, st.kw = d.shape
+            else:
+                d = None
+            if d is not None:
+                keep.append(d)
+                st.data = d.ctypes.data
+        return arr, keep
+
+    def chain_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                          channels: int, steps: Sequence) -> None:
+        n = len(srcs)
+        if not (len(dsts) == n == len(widths) == len(heights)):
+            raise ValueError("srcs, dsts, widths and heights must have the same length")
+        arr, keep = self._steps(steps)
+        sa = (ctypes.c_void_p * n)(*[_addr(s) for s in srcs])
+        da = (ctypes.c_void_p * n)(*[_addr(d) for d in dsts])
+        wa = (ctypes.c_int * n)(*[int(v) for v in widths])
+        ha = (ctypes.c_int * n)(*[int(v) for v in heights])
+        self._check(self._lib.vf_chain_frames_host(self._ctx, sa, da, wa, ha, n, channels, arr, len(steps)))
+        del keep
+
+    def binary_device(self, da: int, db: int, ddst: int, nbytes: int, op: int, stream: int = 0) -> None:
+        """``ddst[i] = op(da[i], db[i])`` over device memory, ``op`` a ``VF_BIN_*``; asynchronous."""
+        self._check(self._lib.vf_binary_device(self._ctx, da or None, db or None, ddst or None, nbytes, op,
+                                               stream or None))
 
     # -- host -> host, asynchronous (page-locked buffers) -----------------------------------
     def invert_frames_async(self, srcs: Sequence, dsts: Sequence, nbytes: Sequence[int]) -> int:
@@ -899,6 +960,43 @@ class Context:
         in the total, not in a stage, as ``jpeg_bench_conv``'s)."""
         return self._jpeg_bench(self._lib.vf_jpeg_bench_rank, self._element_args(op, element, border), "color",
                                 jpegs, quality, subsamp, flags, iters)
+
+    # -- JPEG with a filter chain in place of the inversion (vf_jpeg_chain*); tickets are invert tickets ----
+    def jpeg_chain(self, jpegs: Sequence, steps: Sequence, quality: int, subsamp: int, flags: int = 0) -> list:
+        """decode -> the program's steps -> encode for every JPEG on the GPU; returns bytes.  ``steps``
+        as for ``chain_frames_host`` (``filters.Chain.args[0]``)."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_chain_submit(jpegs, steps, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_chain_submit(self, jpegs: Sequence, steps: Sequence, quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the program (copied by the library: the caller may change its
+        arrays at once); collect with the ``jpeg_invert_result*`` methods."""
+        arr, keep = self._steps(steps)
+        t = self._jpeg_submit("jpeg_chain_submit", self._lib.vf_jpeg_chain_submit, (arr, len(steps)), jpegs, None,
+                              quality, subsamp, flags)
+        del keep
+        return t
+
+    def jpeg_chain_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, steps: Sequence, quality: int,
+                                subsamp: int, flags: int = 0) -> int:
+        """``jpeg_chain_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        arr, keep = self._steps(steps)
+        t = self._jpeg_submit("jpeg_chain_submit_addrs", self._lib.vf_jpeg_chain_submit, (arr, len(steps)), addrs,
+                              sizes, quality, subsamp, flags)
+        del keep
+        return t
+
+    def jpeg_bench_chain(self, jpegs: Sequence, steps: Sequence, quality: int, subsamp: int, flags: int = 0,
+                         iters: int = 10):
+        """``jpeg_bench_invert`` with the program between the decode and the encode (its time is in the
+        total, not in a stage, as ``jpeg_bench_conv``'s)."""
+        arr, keep = self._steps(steps)
+        out = self._jpeg_bench(self._lib.vf_jpeg_bench_chain, (arr, len(steps)), "color", jpegs, quality, subsamp,
+                               flags, iters)
+        del keep
+        return out
 
 
 def jpeg_header(jpeg) -> tuple:

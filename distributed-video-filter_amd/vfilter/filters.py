@@ -449,6 +449,236 @@ def rank_frames(frames: Sequence, rank: Rank, outs: Optional[List] = None, ctx: 
     return outs
 
 
+# -- filter chains: a program of filters between one upload and one download ----------------------
+
+STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
+BINARY_OPS = {"subtract": 0, "add": 1, "absdiff": 2, "min": 3, "max": 4}  # VF_BIN_*
+CHAIN_MAX_STEPS = 8  # VF_CHAIN_MAX_STEPS
+MORPH_OPS = ("erode", "dilate", "open", "close", "gradient", "tophat", "blackhat")
+
+_INVERT_TABLE = bytes(255 - v for v in range(256))
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Combine:
+    """A two-input step of a ``Chain``: ``op(a, b)`` per byte, ``op`` one of "subtract"
+    (``max(a - b, 0)``), "add" (``min(a + b, 255)``), "absdiff", "min", "max" -- ``cv2.subtract``,
+    ``cv2.add``, ``cv2.absdiff``, ``cv2.min``, ``cv2.max`` on uint8.  ``a`` and ``b`` are each a filter
+    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, another ``Combine``), a ``Chain``, or ``None``
+    for the value entering the ``Combine``; both are applied to that value."""
+    op: str
+    op_code: int
+    a: object
+    b: object
+
+    def __init__(self, op: str, a=None, b=None):
+        if op not in BINARY_OPS:
+            raise ValueError(f"combine: op must be one of {sorted(BINARY_OPS)}, not {op!r}")
+        for name, v in (("a", a), ("b", b)):
+            if v is not None and not isinstance(v, _CHAIN_ITEMS + (Chain,)):
+                raise ValueError(f"combine: {name} is a filter value, a Chain or None, not {type(v).__name__}")
+        for name, v in (("op", op), ("op_code", BINARY_OPS[op]), ("a", a), ("b", b)):
+            object.__setattr__(self, name, v)
+
+
+def _unary_step(f, a: int) -> tuple:
+    """The program step of one single-filter value reading value ``a``."""
+    if isinstance(f, Invert):
+        return (STEP_TABLE, a, 0, 0, _INVERT_TABLE, 0, 0)
+    if isinstance(f, Table):
+        return (STEP_TABLE, a, 0, 0, f.planar, 0, 0)
+    if isinstance(f, Kernel):
+        return (STEP_CONV, a, 0, 0, f.weights, f.shift, f.border_code)
+    if isinstance(f, Rank):
+        return (STEP_RANK, a, 0, f.op_code, f.element, 0, f.border_code)
+    raise ValueError(f"chain: a step is Invert, Table, Kernel, Rank, Combine or Chain, not {type(f).__name__}")
+
+
+def _check_program(steps: Sequence[tuple]) -> None:
+    """The structure of a program (csrc/vf_chain_plan.h validate), as ``ValueError``s."""
+    n = len(steps)
+    if n < 1:
+        raise ValueError("chain: an empty program")
+    if n > CHAIN_MAX_STEPS:
+        raise ValueError(f"chain: a program of {n} steps; at most {CHAIN_MAX_STEPS} (VF_CHAIN_MAX_STEPS)")
+    read = [False] * (n + 1)
+    for i, st in enumerate(steps, 1):
+        kind, a, b = st[0], st[1], st[2]
+        for name, v in (("a", a),) + ((("b", b),) if kind == STEP_BINARY else ()):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError(f"chain: step {i}: operand {name} = {v!r} is not a value")
+            if v >= i:
+                raise ValueError(f"chain: step {i}: operand {name} = {v} is not an earlier value "
+                                 f"(a step reads values 0..{i - 1}; no forward reference)")
+            read[v] = True
+    for v in range(n):
+        if not read[v]:
+            raise ValueError(f"chain: value {v} is read by no step (a dead value)")
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Chain:
+    """A program of filters run on the GPU between one upload and one download (raw frames) or one
+    decode and one encode (JPEG): exactly what running its steps one after the other on whole frames
+    gives, every step with whole-frame borders.
+
+    ``Chain(steps)``: each of ``steps`` -- ``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Combine`` or a
+    nested ``Chain``, which is flattened -- is applied to the result of the one before.
+    ``Chain.program(entries)`` takes the program itself: value 0 is the frame, value i the result of
+    entry i (1-based); an entry is ``(filter value, a)`` or ``(binary op name, a, b)`` with ``a`` and
+    ``b`` earlier values.  At most 8 steps; every value but the last is read.  A bad program raises
+    ``ValueError`` here, before a GPU context exists."""
+    steps: tuple  # (kind, a, b, op, data, shift, border) per step; data: table bytes, weights, element, None
+    family = "chain"
+
+    def __init__(self, steps):
+        if isinstance(steps, _CHAIN_ITEMS + (Chain, Combine)):
+            steps = [steps]
+        prog: List[tuple] = []
+        out = _lower(list(steps), 0, prog)
+        if out != len(prog):  # e.g. Chain([]): nothing to run
+            raise ValueError("chain: an empty program")
+        _check_program(prog)
+        object.__setattr__(self, "steps", tuple(prog))
+
+    @classmethod
+    def program(cls, entries) -> "Chain":
+        prog = []
+        for i, e in enumerate(entries, 1):
+            if not isinstance(e, (tuple, list)) or len(e) not in (2, 3):
+                raise ValueError(f"chain: entry {i} is (filter value, a) or (binary op, a, b)")
+            if len(e) == 3:
+                if e[0] not in BINARY_OPS:
+                    raise ValueError(f"chain: entry {i}: op must be one of {sorted(BINARY_OPS)}, not {e[0]!r}")
+                prog.append((STEP_BINARY, e[1], e[2], BINARY_OPS[e[0]], None, 0, 0))
+            else:
+                prog.append(_unary_step(e[0], e[1]))
+        _check_program(prog)
+        self = object.__new__(cls)
+        object.__setattr__(self, "steps", tuple(prog))
+        return self
+
+    @property
+    def args(self) -> tuple:
+        return (self.steps,)
+
+    @property
+    def table_channels(self) -> int:
+        """3 when a step is a 3-channel table (such a chain takes 3-channel frames only), else 1."""
+        return 3 if any(st[0] == STEP_TABLE and len(st[4]) == 768 for st in self.steps) else 1
+
+    def __len__(self) -> int:
+        return len(self.steps)
+
+
+_CHAIN_ITEMS = (Invert, Table, Kernel, Rank)
+
+
+def _lower(item, cur: int, prog: List[tuple]) -> int:
+    """Append the steps of ``item`` applied to value ``cur``; returns the value that holds the result."""
+    if item is None:
+        return cur
+    if isinstance(item, (list, tuple)):
+        for it in item:
+            cur = _lower(it, cur, prog)
+        return cur
+    if isinstance(item, Chain):  # its program, moved: its value 0 is cur, its value i is base + i
+        base = len(prog)
+        for (kind, a, b, op, data, shift, border) in item.steps:
+            prog.append((kind, base + a if a else cur, (base + b if b else cur) if kind == STEP_BINARY else 0, op, data,
+                         shift, border))
+        return len(prog)
+    if isinstance(item, Combine):
+        va = _lower(item.a, cur, prog)
+        vb = _lower(item.b, cur, prog)
+        prog.append((STEP_BINARY, va, vb, item.op_code, None, 0, 0))
+        return len(prog)
+    prog.append(_unary_step(item, cur))
+    return len(prog)
+
+
+def Morph(op: str, element=None, iterations: int = 1, border: str = "constant") -> Chain:
+    """``cv2.morphologyEx(src, op, element, iterations=iterations)`` as a ``Chain``.  With E^n / D^n
+    for n successive erosions / dilations by ``element``: "erode" E^n, "dilate" D^n, "open" D^n(E^n x),
+    "close" E^n(D^n x), "gradient" subtract(D^n x, E^n x), "tophat" subtract(x, open),
+    "blackhat" subtract(close, x).  ``iterations`` is limited by the chain's 8 steps."""
+    if op not in MORPH_OPS:
+        raise ValueError(f"morphology_ex: op must be one of {list(MORPH_OPS)}, not {op!r}")
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 1:
+        raise ValueError(f"morphology_ex: iterations must be a positive integer, not {iterations!r}")
+    n = int(iterations)
+    need = {"erode": n, "dilate": n, "open": 2 * n, "close": 2 * n}.get(op, 2 * n + 1)
+    if need > CHAIN_MAX_STEPS:
+        raise ValueError(f"morphology_ex: {op} with iterations={n} is a chain of {need} steps; a chain has at most "
+                         f"{CHAIN_MAX_STEPS} (VF_CHAIN_MAX_STEPS), so iterations is limited by that cap")
+    e, d = [Rank.erode(element, border)] * n, [Rank.dilate(element, border)] * n
+    if op == "erode":
+        return Chain(e)
+    if op == "dilate":
+        return Chain(d)
+    if op == "open":
+        return Chain(e + d)
+    if op == "close":
+        return Chain(d + e)
+    if op == "gradient":
+        return Chain([Combine("subtract", Chain(d), Chain(e))])
+    if op == "tophat":
+        return Chain([Combine("subtract", None, Chain(e + d))])
+    return Chain([Combine("subtract", Chain(d + e), None)])
+
+
+def _as_chain(c) -> Chain:
+    return c if isinstance(c, Chain) else Chain(c)
+
+
+def _chain_frame(name: str, a, c: Chain) -> np.ndarray:
+    a = _conv_frame(name, a)
+    if c.table_channels == 3 and (a.ndim != 3 or a.shape[2] != 3):
+        raise ValueError(f"{name}: the chain has a 3-channel table; frames are H x W x 3, not shape {a.shape}")
+    return a
+
+
+def chain(src: np.ndarray, steps, dst: Optional[np.ndarray] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """Run a ``Chain`` (or a list of steps, as for ``Chain``) on a uint8 ``H x W`` or ``H x W x 3`` frame
+    with one upload and one download.  ``dst`` as for ``filter2d``, and it may be ``src``."""
+    c = _as_chain(steps)
+    src = np.ascontiguousarray(_chain_frame("chain", src, c))
+    dst = _rank_dst("chain", src, dst)
+    channels = 1 if src.ndim == 2 else src.shape[2]
+    if src.size:
+        (ctx or get_context()).chain_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, *c.args)
+    return dst
+
+
+def chain_frames(frames: Sequence, chain, outs: Optional[List] = None, ctx: Optional[Context] = None) -> List:
+    """A ``Chain`` over separately stored frames of one channel count and mixed sizes in one call.
+    Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
+    c = _as_chain(chain)
+    srcs = [np.ascontiguousarray(_chain_frame("chain_frames", f, c)) for f in frames]
+    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
+    if len(chans) > 1:
+        raise ValueError("chain_frames: the frames of one call have one channel count")
+    if outs is None:
+        outs = [np.empty_like(s) for s in srcs]
+    elif len(outs) != len(srcs) or any(o.shape != s.shape or o.dtype != np.uint8 or not o.flags.c_contiguous
+                                       for o, s in zip(outs, srcs)):
+        raise ValueError("chain_frames: outs must be C-contiguous uint8 arrays of the frames' shapes")
+    live = [(s, o) for s, o in zip(srcs, outs) if s.size]
+    if live:
+        (ctx or get_context()).chain_frames_host([s for s, _ in live], [o for _, o in live],
+                                                 [s.shape[1] for s, _ in live], [s.shape[0] for s, _ in live],
+                                                 chans.pop(), *c.args)
+    return outs
+
+
+def morphology_ex(src: np.ndarray, op: str, element=None, iterations: int = 1, dst: Optional[np.ndarray] = None,
+                  border: str = "constant", ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.morphologyEx(src, op, element, iterations=iterations)`` on uint8 ``H x W`` or
+    ``H x W x 3`` input, ``op`` one of "erode", "dilate", "open", "close", "gradient", "tophat",
+    "blackhat" (``Morph`` has the programs).  Equal to cv2 for the default border, "constant"."""
+    return chain(src, Morph(op, element, iterations, border), dst, ctx)
+
+
 def invert_frames(frames: Sequence, outs: Optional[List] = None,
                   ctx: Optional[Context] = None) -> List:
     """Invert separately stored frames (ndarrays or bytes-likes; mixed sizes allowed) with

@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import Invert, Kernel, Rank, Table
+from .filters import Invert, Kernel, Morph, Rank, Table, _as_chain
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -205,6 +205,38 @@ class TurboJPEG:
     def median_blur_batch(self, jpeg_bufs: Sequence, ksize: int, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
                           flags: int = 0) -> List[bytes]:
         return self.filter_batch(jpeg_bufs, Rank.median(ksize), quality, jpeg_subsample, flags)
+
+    # -- a filter chain (vfilter.filters.Chain) between one decode and one encode ------------------------
+    def chain(self, jpeg_buf, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(run(decode(jpeg_buf), chain))`` on the GPU with one decode and one encode: the steps
+        in between see the pixels, not JPEG generations.  ``chain`` is a ``Chain`` or a list of steps,
+        as for ``vfilter.chain``; every step works on the decoded BGR frame."""
+        return self.filter_batch([jpeg_buf], _as_chain(chain), quality, jpeg_subsample, flags)[0]
+
+    def chain_batch(self, jpeg_bufs: Sequence, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                    flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, _as_chain(chain), quality, jpeg_subsample, flags)
+
+    def chain_batch_submit(self, jpeg_bufs: Sequence, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                           flags: int = 0) -> int:
+        """The program is copied, with its tables, kernels and elements: the caller may change them at once."""
+        return self.filter_batch_submit(jpeg_bufs, _as_chain(chain), quality, jpeg_subsample, flags)
+
+    def chain_batch_submit_addrs(self, addrs, sizes, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                                 flags: int = 0) -> int:
+        return self.filter_batch_submit_addrs(addrs, sizes, _as_chain(chain), quality,
+                                              jpeg_subsample, flags)
+
+    def morphology_ex(self, jpeg_buf, op: str, element=None, iterations: int = 1, border: str = "constant",
+                      quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(cv2.morphologyEx(decode(jpeg_buf), op, element, iterations=iterations))`` on the GPU;
+        the arguments as for ``vfilter.morphology_ex``."""
+        return self.filter_batch([jpeg_buf], Morph(op, element, iterations, border), quality, jpeg_subsample, flags)[0]
+
+    def morphology_ex_batch(self, jpeg_bufs: Sequence, op: str, element=None, iterations: int = 1,
+                            border: str = "constant", quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                            flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, Morph(op, element, iterations, border), quality, jpeg_subsample, flags)
 
     def invert_batch_result_into_addrs(self, ticket: int, out_addrs, cap: int):
         """(sizes, {i: JPEG that did not fit}): each result written at ``out_addrs[i]`` (``cap``

@@ -426,6 +426,81 @@ int vf_jpeg_bench_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
                        int op, const uint8_t *element, int kw, int kh, int border, int quality,
                        int subsamp, int flags, int iters, float *ms, float *stage_ms);
 
+/* ---- filter chains (cv2.morphologyEx, difference of blurs, ...) -----------------------------
+ * A program is a straight-line list of 1 .. VF_CHAIN_MAX_STEPS steps over values.
+ * Value 0 is the input frame (uint8, 1 or 3 interleaved channels, packed rows), value i the result
+ * of step i (1-based), and the program's result is the last step's value.  Each step names its
+ * operand `a`, a binary step `b` as well; operands are earlier values.  Every step sees
+ * whole-frame borders, so the result is exactly what running the steps one after the other on
+ * whole frames gives.  Step kinds:
+ *   VF_STEP_TABLE   cv2.LUT: `data` is channels x 256 bytes, planar (as for vf_lut_*)
+ *   VF_STEP_CONV    cv2.filter2D: `data` is kw * kh int16 weights, with `shift` and `border`
+ *   VF_STEP_RANK    `op` a VF_RANK_*: `data` is the kw * kh element bytes, with `border`
+ *   VF_STEP_BINARY  `op` a VF_BIN_*, per byte on the values `a` and `b`:
+ *                   SUBTRACT max(a - b, 0), ADD min(a + b, 255), ABSDIFF |a - b|, MIN, MAX
+ *                   (cv2.subtract, cv2.add, cv2.absdiff, cv2.min, cv2.max on uint8)
+ * `data` is a HOST pointer, read during the call only.  VF_E_INVALID, before any GPU work: a step
+ * that reads a later value or itself, a value other than the last that no step reads, a 3-channel
+ * table on 1-channel frames, more than VF_CHAIN_MAX_STEPS steps, and anything the single-filter
+ * entry points refuse for a table, a kernel or an element. */
+#define VF_STEP_TABLE  0
+#define VF_STEP_CONV   1
+#define VF_STEP_RANK   2
+#define VF_STEP_BINARY 3
+#define VF_BIN_SUBTRACT 0
+#define VF_BIN_ADD      1
+#define VF_BIN_ABSDIFF  2
+#define VF_BIN_MIN      3
+#define VF_BIN_MAX      4
+#define VF_CHAIN_MAX_STEPS 8
+
+typedef struct vf_step {
+  int kind;         /* a VF_STEP_* */
+  int a, b;         /* operand values; b for VF_STEP_BINARY only */
+  int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_* */
+  const void *data; /* the table, the int16 weights or the element (host memory) */
+  int kw, kh;       /* VF_STEP_CONV, VF_STEP_RANK */
+  int shift;        /* VF_STEP_CONV */
+  int border;       /* VF_STEP_CONV, VF_STEP_RANK: a VF_BORDER_* */
+  int channels;     /* VF_STEP_TABLE: 1 or 3 */
+} vf_step;
+
+/* Enqueue ddst[i] = op(da[i], db[i]) over nbytes of device memory on `stream`, op a VF_BIN_*.
+ * Returns after the launch (does not synchronise); each pointer at any alignment.  ddst == da or
+ * ddst == db exactly is allowed; a partial overlap of ddst with either, a NULL pointer or an
+ * unknown op is VF_E_INVALID.  nbytes == 0 is VF_OK and writes nothing. */
+int vf_binary_device(vf_ctx *ctx, const void *da, const void *db, void *ddst, size_t nbytes,
+                     int op, void *stream);
+
+/* The program on `n` separately allocated host frames (srcs[i] -> dsts[i], widths[i] x heights[i]
+ * x channels), synchronous, as vf_conv_frames_host: srcs[i] == dsts[i] is allowed; a frame larger
+ * than the context's staging is cut into bands of rows with the program's total vertical reach R
+ * (the largest summed radius along a path) as halo; VF_E_INVALID when 2 R + 1 rows of a frame do
+ * not fit it.  Intermediate values live in device scratch of the context, allocated by the first
+ * call that needs them and freed with the context. */
+int vf_chain_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                         const int *widths, const int *heights, int n, int channels,
+                         const vf_step *steps, int nsteps);
+
+/* vf_jpeg_invert with the program in place of the inversion: decode -> the steps -> encode on
+ * the GPU with one decode and one encode, on the decoded BGR frame (3 channels).  A program that
+ * folds to a single table runs in the fused colour stage, as vf_jpeg_lut does. */
+int vf_jpeg_chain(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                  const vf_step *steps, int nsteps, int quality, int subsamp, int flags,
+                  uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the program (copied, with every table, kernel and element: the
+ * caller may reuse them at once).  The ticket is an invert ticket: collect with
+ * vf_jpeg_invert_query / _wait / _fetch / _scatter. */
+int vf_jpeg_chain_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                         const vf_step *steps, int nsteps, int quality, int subsamp, int flags,
+                         uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the program between the decode and the encode. */
+int vf_jpeg_bench_chain(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                        const vf_step *steps, int nsteps, int quality, int subsamp, int flags,
+                        int iters, float *ms, float *stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

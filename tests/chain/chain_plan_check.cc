@@ -1,0 +1,469 @@
+// chain_plan_check.cc — csrc/vf_chain_plan.h on the CPU (tests/test_chain_plan.py builds this with
+// -fsanitize=address,undefined and reads the JSON line it prints).
+//   validate   every kind of invalid program is refused with its reason, the valid ones pass
+//   fold       a composed table equals the tables in sequence; what must not fold does not
+//   buffers    the schedule simulated: no live value overwritten, no neighbourhood step writes its
+//              source, the result buffer reported, the count within live values + 1
+//   grid       a scalar model of each step run band by band (vf_conv_bands.h with ry = R), reading
+//              only rows the plan says exist, borders in frame coordinates, equals the whole frame
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "vf_chain_plan.h"
+#include "vf_conv_bands.h"
+#include "vf_conv_border.h"
+
+using namespace vf::chain;
+
+namespace {
+
+int g_failed = 0;
+#define CHECK(c)                                                   \
+  do {                                                             \
+    if (!(c)) {                                                    \
+      ++g_failed;                                                  \
+      std::fprintf(stderr, "line %d: %s\n", __LINE__, #c);         \
+    }                                                              \
+  } while (0)
+
+enum { kErode = 0, kDilate = 1, kMedian = 2 };  // VF_RANK_*
+
+Step table1(int a, int seed) {
+  Step s;
+  s.kind = kTable, s.a = a, s.channels = 1;
+  s.table.resize(256);
+  for (int v = 0; v < 256; ++v) s.table[v] = (uint8_t)(seed == 0 ? 255 - v : seed == 1 ? (v > 24 ? 255 : 0) : (v * 7 + seed) & 255);
+  return s;
+}
+Step table3(int a) {
+  Step s;
+  s.kind = kTable, s.a = a, s.channels = 3;
+  s.table.resize(768);
+  for (int c = 0; c < 3; ++c)
+    for (int v = 0; v < 256; ++v) s.table[c * 256 + v] = (uint8_t)((v * (3 + 2 * c) + 11 * c) & 255);
+  return s;
+}
+Step rank(int a, int op, int kw, int kh, int border, bool corner = false) {
+  Step s;
+  s.kind = kRank, s.a = a, s.op = op, s.kw = kw, s.kh = kh, s.border = border;
+  s.element.assign((size_t)kw * kh, corner ? 0 : 1);
+  if (corner) s.element[0] = 1;
+  return s;
+}
+Step conv(int a, int k, int border) {  // binomial k x k
+  Step s;
+  s.kind = kConv, s.a = a, s.kw = k, s.kh = k, s.border = border;
+  const int b3[3] = {1, 2, 1}, b5[5] = {1, 4, 6, 4, 1};
+  for (int j = 0; j < k; ++j)
+    for (int i = 0; i < k; ++i) s.weights.push_back((int16_t)(k == 3 ? b3[j] * b3[i] : b5[j] * b5[i]));
+  s.shift = k == 3 ? 4 : 8;
+  return s;
+}
+Step bin(int op, int a, int b) {
+  Step s;
+  s.kind = kBinary, s.op = op, s.a = a, s.b = b;
+  return s;
+}
+
+Program edges(int border) {  // median3 -> gradient rect3 -> threshold: R = 2
+  Program p;
+  p.steps = {rank(0, kMedian, 3, 3, vf::conv::kReplicate), rank(1, kDilate, 3, 3, border), rank(1, kErode, 3, 3, border),
+             bin(kSubtract, 2, 3), table1(4, 1)};
+  return p;
+}
+Program blackhat3_it2(int border) {  // subtract(E E D D x, x): R = 4, 5 steps
+  Program p;
+  p.steps = {rank(0, kDilate, 3, 3, border), rank(1, kDilate, 3, 3, border), rank(2, kErode, 3, 3, border),
+             rank(3, kErode, 3, 3, border), bin(kSubtract, 4, 0)};
+  return p;
+}
+Program diamond(int border) {  // add(erode rect7 x, x): value 0 read with reach 3 and reach 0
+  Program p;
+  p.steps = {rank(0, kErode, 7, 7, border), bin(kAdd, 1, 0)};
+  return p;
+}
+Program dog(int border) {
+  Program p;
+  p.steps = {conv(0, 3, border), conv(0, 5, border), bin(kAbsdiff, 1, 2), table1(3, 5)};
+  return p;
+}
+Program pointwise() {
+  Program p;
+  p.steps = {table1(0, 0), table3(1), table1(2, 0)};
+  return p;
+}
+Program eight(int border) {
+  Program p;
+  p.steps = {rank(0, kErode, 3, 3, border), rank(1, kDilate, 3, 3, border), bin(kSubtract, 0, 2), table1(3, 9),
+             conv(4, 3, border), rank(5, kMedian, 3, 3, vf::conv::kReplicate), bin(kMax, 6, 1), bin(kAdd, 7, 3)};
+  return p;
+}
+Program corner_gradient(int border) {
+  Program p;
+  p.steps = {rank(0, kDilate, 5, 5, border, true), rank(0, kErode, 5, 5, border, true), bin(kSubtract, 2, 1)};
+  return p;
+}
+
+// ---- validate ---------------------------------------------------------------------------------------
+
+int g_checked = 0;
+void refused(const Program &p, int channels, const char *reason) {
+  std::string why;
+  ++g_checked;
+  const bool ok = validate(p, channels, &why);
+  if (ok || why.find(reason) == std::string::npos) {
+    ++g_failed;
+    std::fprintf(stderr, "expected a refusal with \"%s\", got %s \"%s\"\n", reason, ok ? "valid" : "invalid", why.c_str());
+  }
+}
+void accepted(const Program &p, int channels) {
+  std::string why;
+  ++g_checked;
+  if (!validate(p, channels, &why)) {
+    ++g_failed;
+    std::fprintf(stderr, "expected valid, got \"%s\"\n", why.c_str());
+  }
+}
+
+int run_validate() {
+  const int B = vf::conv::kConstant;
+  for (int ch : {1, 3}) {
+    accepted(edges(B), ch), accepted(blackhat3_it2(B), ch), accepted(diamond(B), ch), accepted(dog(B), ch);
+    accepted(eight(B), ch), accepted(corner_gradient(B), ch);
+  }
+  accepted(pointwise(), 3);
+  refused(pointwise(), 1, "3-channel table on 1-channel frames");
+  Program p;
+  refused(p, 3, "empty program");
+  p = eight(B);
+  p.steps.push_back(table1(8, 0));
+  refused(p, 3, "9 steps; at most 8");
+  p = diamond(B);
+  p.steps[0].a = 1;  // reads itself
+  refused(p, 3, "step 1: operand a = 1 is not an earlier value");
+  p = diamond(B);
+  p.steps[0].a = 2;  // reads a later value
+  refused(p, 3, "operand a = 2 is not an earlier value");
+  p = diamond(B);
+  p.steps[1].b = 2;
+  refused(p, 3, "step 2: operand b = 2 is not an earlier value");
+  p = diamond(B);
+  p.steps[1].a = -1;
+  refused(p, 3, "not an earlier value");
+  p = diamond(B);
+  p.steps[1].a = 0;  // add(x, x): value 1 is dead
+  refused(p, 3, "value 1 is read by no step");
+  p = edges(B);
+  p.steps[3].b = 2;  // subtract(dilate, dilate): the erosion is dead
+  refused(p, 3, "value 3 is read by no step");
+  p = diamond(B);
+  p.steps[1].op = 5;
+  refused(p, 3, "unknown binary op 5");
+  p = diamond(B);
+  p.steps[1].kind = 4;
+  refused(p, 3, "unknown kind 4");
+  p = diamond(B);
+  p.steps[0].kh = 9;
+  refused(p, 3, "sides are odd and at most 7");
+  p = diamond(B);
+  p.steps[0].kw = 4;
+  refused(p, 3, "sides are odd and at most 7");
+  p = diamond(B);
+  p.steps[0].element.pop_back();
+  refused(p, 3, "kw x kh entries");
+  p = pointwise();
+  p.steps[1].channels = 2;
+  refused(p, 3, "a table has 1 or 3 channels");
+  p = pointwise();
+  p.steps[0].table.resize(100);
+  refused(p, 3, "channels x 256 bytes");
+  refused(diamond(B), 2, "frames have 1 or 3 channels");
+  // a step's b is not an operand unless the step is binary: any b passes for the others
+  p = diamond(B);
+  p.steps[0].b = 77;
+  accepted(p, 3);
+  std::printf("{\"checked\": %d, \"failed\": %d}\n", g_checked, g_failed);
+  return g_failed ? 1 : 0;
+}
+
+// ---- fold -------------------------------------------------------------------------------------------
+
+uint8_t through(const Step &t, int c, uint8_t v) { return t.table[(t.channels == 3 ? 256 * c : 0) + v]; }
+
+int run_fold() {
+  const int B = vf::conv::kConstant;
+  int tables = 0;
+  {  // invert -> 3-channel curves -> invert: one 3-channel table, equal to the sequence
+    const Program p = pointwise(), f = fold(p);
+    CHECK(f.size() == 1 && f.steps[0].kind == kTable && f.steps[0].a == 0 && f.steps[0].channels == 3);
+    CHECK(single_kind(f) == kTable);
+    for (int c = 0; c < 3 && f.size() == 1; ++c)
+      for (int v = 0; v < 256; ++v, ++tables)
+        CHECK(through(f.steps[0], c, (uint8_t)v) ==
+              through(p.steps[2], c, through(p.steps[1], c, through(p.steps[0], c, (uint8_t)v))));
+  }
+  {  // two 1-channel tables stay 1 channel
+    Program p;
+    p.steps = {table1(0, 3), table1(1, 4)};
+    const Program f = fold(p);
+    CHECK(f.size() == 1 && f.steps[0].channels == 1 && f.steps[0].table.size() == 256);
+    for (int v = 0; v < 256 && f.size() == 1; ++v, ++tables)
+      CHECK(f.steps[0].table[v] == p.steps[1].table[p.steps[0].table[v]]);
+  }
+  {  // 3-channel then 1-channel
+    Program p;
+    p.steps = {table3(0), table1(1, 4)};
+    const Program f = fold(p);
+    CHECK(f.size() == 1 && f.steps[0].channels == 3);
+    for (int c = 0; c < 3 && f.size() == 1; ++c)
+      for (int v = 0; v < 256; ++v, ++tables)
+        CHECK(through(f.steps[0], c, (uint8_t)v) == p.steps[1].table[p.steps[0].table[c * 256 + v]]);
+  }
+  {  // a table with two readers is kept; the tables after the binary step fold, operands renumbered
+    Program p;
+    p.steps = {table1(0, 3), table1(1, 4), bin(kAdd, 1, 2), table1(3, 5), table1(4, 0)};
+    const Program f = fold(p);
+    std::string why;
+    CHECK(validate(f, 1, &why));
+    CHECK(f.size() == 4 && f.steps[0].kind == kTable && f.steps[1].kind == kTable && f.steps[1].a == 1);
+    CHECK(f.steps[2].kind == kBinary && f.steps[2].a == 1 && f.steps[2].b == 2 && f.steps[3].a == 3);
+    for (int v = 0; v < 256 && f.size() == 4; ++v, ++tables)
+      CHECK(f.steps[3].table[v] == p.steps[4].table[p.steps[3].table[v]]);
+    CHECK(single_kind(f) == -1);
+  }
+  {  // a table read by a neighbourhood step is kept; programs without tables are unchanged
+    Program p;
+    p.steps = {table1(0, 0), rank(1, kErode, 3, 3, B), table1(2, 0)};
+    CHECK(fold(p).size() == 3);
+    CHECK(fold(blackhat3_it2(B)).size() == 5 && fold(diamond(B)).size() == 2);
+    CHECK(fold(edges(B)).size() == 5 && fold(eight(B)).size() == 8);
+    Program one;
+    one.steps = {rank(0, kErode, 3, 3, B)};
+    CHECK(single_kind(one) == kRank);
+    one.steps = {conv(0, 3, B)};
+    CHECK(single_kind(one) == kConv);
+    one.steps = {bin(kAdd, 0, 0)};
+    CHECK(single_kind(one) == -1);
+  }
+  std::printf("{\"tables\": %d, \"failed\": %d}\n", tables, g_failed);
+  return g_failed ? 1 : 0;
+}
+
+// ---- buffers ----------------------------------------------------------------------------------------
+
+int run_buffers() {
+  const int B = vf::conv::kConstant;
+  Program same;
+  same.steps = {bin(kAdd, 0, 0), bin(kMax, 1, 1)};
+  Program fan;  // value 0 stays live to the end
+  fan.steps = {rank(0, kErode, 3, 3, B), rank(0, kDilate, 3, 3, B), conv(0, 3, B), bin(kAdd, 1, 2), bin(kMax, 4, 3),
+               bin(kMin, 5, 0)};
+  const std::vector<Program> ps = {edges(B),  blackhat3_it2(B), diamond(B),          dog(B), pointwise(), fold(pointwise()),
+                                   eight(B), corner_gradient(B), same, fan};
+  int programs = 0, max_count = 0, in_place = 0;
+  for (const Program &p : ps) {
+    ++programs;
+    const int n = p.size();
+    const Buffers b = assign_buffers(p);
+    CHECK((int)b.of.size() == n + 1 && b.of[0] == 0 && b.result == b.of[n]);
+    std::vector<int> last(n + 1, 0);
+    for (int i = 1; i <= n; ++i) {
+      last[p.steps[i - 1].a] = i;
+      if (p.steps[i - 1].kind == kBinary) last[p.steps[i - 1].b] = i;
+    }
+    last[n] = n + 1;
+    std::vector<int> holds(b.count, -1);  // the value each buffer holds
+    holds[0] = 0;
+    int max_live = 1;
+    for (int i = 1; i <= n; ++i) {
+      const Step &s = p.steps[i - 1];
+      const int k = b.of[i];
+      CHECK(k >= 0 && k < b.count);
+      if (k < 0 || k >= b.count) break;
+      // the operands are where the plan says, not overwritten since
+      CHECK(holds[b.of[s.a]] == s.a);
+      if (s.kind == kBinary) CHECK(holds[b.of[s.b]] == s.b);
+      if (is_neighbourhood(s)) CHECK(k != b.of[s.a]);  // never writes the buffer it reads
+      const int u = holds[k];
+      if (u >= 0 && last[u] >= i) {  // overwrites a value some step from i on reads: only in place
+        CHECK(last[u] == i && !is_neighbourhood(s) && reads(s, u));
+        ++in_place;
+      }
+      holds[k] = i;
+      int live = 1;  // value i and every earlier value still to be read (by step i too)
+      for (int v = 0; v < i; ++v) live += last[v] >= i;
+      if (live > max_live) max_live = live;
+    }
+    CHECK(holds[b.result] == n);
+    CHECK(b.count <= max_live + 1);
+    if (b.count > max_count) max_count = b.count;
+  }
+  CHECK(assign_buffers(blackhat3_it2(B)).count <= 3 && assign_buffers(edges(B)).count <= 3);
+  CHECK(assign_buffers(diamond(B)).count == 2 && assign_buffers(fold(pointwise())).count == 1);
+  std::printf("{\"programs\": %d, \"max_count\": %d, \"in_place\": %d, \"failed\": %d}\n", programs, max_count, in_place,
+              g_failed);
+  return g_failed ? 1 : 0;
+}
+
+// ---- grid: a scalar model of the steps, band by band ----------------------------------------------
+
+struct Val {
+  int lo = 0, hi = 0;  // the rows present
+  std::vector<uint8_t> d;
+};
+
+int g_bad_reads = 0;
+
+struct Frame {
+  int W, H, C;
+  size_t row() const { return (size_t)W * C; }
+};
+
+// byte (y, x, c) of a value, y and x already resolved into the frame
+uint8_t at(const Val &v, const Frame &f, int y, int x, int c) {
+  if (y < v.lo || y >= v.hi) {  // a row the plan did not say exists
+    ++g_bad_reads;
+    return 0x5A;
+  }
+  return v.d[(size_t)(y - v.lo) * f.row() + (size_t)x * f.C + c];
+}
+
+int round_shift(int acc, int shift) {  // round half to even
+  if (shift == 0) return acc;
+  const int fl = acc >> shift, r = acc & ((1 << shift) - 1), h = 1 << (shift - 1);
+  return fl + ((r > h) || (r == h && (fl & 1)));
+}
+
+Val run_step(const Step &s, const std::vector<Val> &vals, const Frame &f, Rows out) {
+  Val o;
+  o.lo = out.lo, o.hi = out.hi;
+  o.d.assign((size_t)(out.hi - out.lo) * f.row(), 0);
+  for (int y = out.lo; y < out.hi; ++y)
+    for (int x = 0; x < f.W; ++x)
+      for (int c = 0; c < f.C; ++c) {
+        int r = 0;
+        if (s.kind == kTable) {
+          r = through(s, c, at(vals[s.a], f, y, x, c));
+        } else if (s.kind == kBinary) {
+          const int a = at(vals[s.a], f, y, x, c), b = at(vals[s.b], f, y, x, c);
+          r = s.op == kSubtract ? a - b : s.op == kAdd ? a + b : s.op == kAbsdiff ? std::abs(a - b) : s.op == kMin ? (a < b ? a : b) : (a > b ? a : b);
+        } else {
+          int acc = 0, mn = 255, mx = 0, cnt = 0;
+          int med[49];
+          for (int j = 0; j < s.kh; ++j)
+            for (int i = 0; i < s.kw; ++i) {
+              if (s.kind == kRank && !s.element[(size_t)j * s.kw + i]) continue;
+              const int by = vf::conv::border_index(y + j - s.kh / 2, f.H, s.border);  // FRAME coordinates
+              const int bx = vf::conv::border_index(x + i - s.kw / 2, f.W, s.border);
+              if (by < 0 || bx < 0) continue;  // constant: reads 0 (conv), left out of the set (rank)
+              const int v = at(vals[s.a], f, by, bx, c);
+              acc += s.kind == kConv ? v * s.weights[(size_t)j * s.kw + i] : 0;
+              mn = v < mn ? v : mn, mx = v > mx ? v : mx;
+              med[cnt++] = v;
+            }
+          if (s.kind == kConv) r = round_shift(acc, s.shift);
+          else if (s.op == kErode) r = mn;
+          else if (s.op == kDilate) r = mx;
+          else {
+            for (int a = 1; a < cnt; ++a)
+              for (int b = a; b > 0 && med[b - 1] > med[b]; --b) std::swap(med[b - 1], med[b]);
+            r = med[cnt / 2];
+          }
+        }
+        o.d[(size_t)(y - out.lo) * f.row() + (size_t)x * f.C + c] = (uint8_t)(r < 0 ? 0 : r > 255 ? 255 : r);
+      }
+  return o;
+}
+
+// rows [y0, y1) of the program's result from rows [s0, s1) of the frame
+Val run_band(const Program &p, const Frame &f, const std::vector<uint8_t> &img, int y0, int y1, int s0, int s1) {
+  const std::vector<Rows> need = rows_needed(p, f.H, y0, y1);
+  std::vector<Val> vals(p.size() + 1);
+  CHECK(need[0].lo >= s0 && need[0].hi <= s1);  // the upload covers what value 0 must hold
+  vals[0].lo = need[0].lo, vals[0].hi = need[0].hi;
+  vals[0].d.assign(img.begin() + (size_t)need[0].lo * f.row(), img.begin() + (size_t)need[0].hi * f.row());
+  for (int i = 1; i <= p.size(); ++i) {
+    CHECK(need[i].lo >= 0 && need[i].lo < need[i].hi && need[i].hi <= f.H);
+    CHECK(need[i].lo >= s0 && need[i].hi <= s1);  // every value fits the band's buffer at the band's row origin
+    vals[i] = run_step(p.steps[i - 1], vals, f, need[i]);
+  }
+  return vals[p.size()];
+}
+
+int run_grid() {
+  int cases = 0, errors = 0, multi_band = 0, bands_run = 0;
+  unsigned seed = 12345;
+  for (int which = 0; which < 3; ++which)
+    for (int border = 0; border < 3; ++border) {
+      const Program p = which == 0 ? edges(border) : which == 1 ? blackhat3_it2(border) : diamond(border);
+      const int R = reach(p);
+      CHECK(R == (which == 0 ? 2 : which == 1 ? 4 : 3));
+      for (int H : {1, 2, 3, 9, 40})
+        for (int W : {1, 5})
+          for (int C : {1, 3}) {
+            const Frame f{W, H, C};
+            std::vector<uint8_t> img((size_t)H * f.row());
+            for (uint8_t &b : img) b = (uint8_t)((seed = seed * 1664525u + 1013904223u) >> 24);
+            const Val whole = run_band(p, f, img, 0, H, 0, H);
+            CHECK(whole.lo == 0 && whole.hi == H);
+            // capacities: from one row short of "one row + halo" up to the whole frame and a bit
+            const int need_rows = 2 * R + 1 < H ? 2 * R + 1 : H;
+            for (int rows = need_rows - 1; rows <= H + 1; ++rows)
+              for (int extra : {0, 1}) {
+                if (rows < 0 || (rows == need_rows - 1 && extra)) continue;
+                const size_t cap = (size_t)rows * f.row() + (extra ? f.row() - 1 : 0);
+                std::vector<vf::conv::Band> bs;
+                ++cases;
+                if (!vf::conv::bands(W, H, C, R, cap, &bs)) {
+                  ++errors;
+                  CHECK(bs.empty() && rows < need_rows);  // an error, not an endless list; only below 2R + 1 rows
+                  continue;
+                }
+                CHECK(rows >= need_rows);
+                multi_band += bs.size() > 1;
+                int next = 0;
+                for (const vf::conv::Band &b : bs) {
+                  CHECK(b.y0 == next && b.y1 > b.y0);
+                  next = b.y1;
+                  CHECK((size_t)(b.s1 - b.s0) * f.row() <= cap);
+                  const Val got = run_band(p, f, img, b.y0, b.y1, b.s0, b.s1);
+                  ++bands_run;
+                  CHECK(got.lo == b.y0 && got.hi == b.y1);
+                  CHECK(std::memcmp(got.d.data(), whole.d.data() + (size_t)b.y0 * f.row(), got.d.size()) == 0);
+                }
+                CHECK(next == H);
+              }
+          }
+    }
+  CHECK(g_bad_reads == 0);
+  std::printf("{\"cases\": %d, \"errors\": %d, \"multi_band\": %d, \"bands\": %d, \"bad_reads\": %d, \"failed\": %d}\n", cases,
+              errors, multi_band, bands_run, g_bad_reads, g_failed);
+  return g_failed ? 1 : 0;
+}
+
+// rows PROGRAM H y0 y1: the plan's rows of every value, for the tests that name figures
+int run_rows(const char *name, int H, int y0, int y1) {
+  const int B = vf::conv::kConstant;
+  const Program p = !std::strcmp(name, "edges") ? edges(B) : !std::strcmp(name, "blackhat3_it2") ? blackhat3_it2(B) : diamond(B);
+  const std::vector<Rows> need = rows_needed(p, H, y0, y1);
+  std::printf("{\"reach\": %d, \"rows\": [", reach(p));
+  for (size_t v = 0; v < need.size(); ++v) std::printf("%s[%d, %d]", v ? ", " : "", need[v].lo, need[v].hi);
+  std::printf("]}\n");
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  const std::string mode = argc > 1 ? argv[1] : "";
+  if (mode == "validate") return run_validate();
+  if (mode == "fold") return run_fold();
+  if (mode == "buffers") return run_buffers();
+  if (mode == "grid") return run_grid();
+  if (mode == "rows" && argc == 6) return run_rows(argv[2], std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]));
+  std::fprintf(stderr, "usage: chain_plan_check validate | fold | buffers | grid | rows PROGRAM H y0 y1\n");
+  return 2;
+}
