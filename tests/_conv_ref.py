@@ -100,3 +100,22 @@ def kernel_set():
         "random3x5": (r35, 3),
     }
 
+
+
+OBLONG_SIDES = [(1, 3), (1, 7), (7, 1), (5, 1), (7, 3), (3, 7), (5, 3), (1, 1)]  # kh x kw
+
+
+def oblong_set():
+    """Kernels that are not square, most of them wider than tall, as name "khxkw" -> (int weights,
+    shift): random signed weights, so a flip, a transpose or a kernel put off-centre into the
+    square the GPU kernel is compiled for cannot pass.  7x3 sums |K| above 128 (the wide form)."""
+    out = {}
+    for kh, kw in OBLONG_SIDES:
+        rng = np.random.default_rng([16, kh, kw])
+        m = 60 if (kh, kw) == (7, 3) else 9
+        k = rng.integers(-m, m + 1, (kh, kw))
+        if kh * kw == 1:
+            k[0, 0] = 3  # 1x1: a gain of 3 / 8
+        out["%dx%d" % (kh, kw)] = (k, 8 if m == 60 else 1 + (kh + kw) % 3)
+    assert np.abs(out["7x3"][0]).sum() > 128 >= np.abs(out["1x7"][0]).sum()
+    return out

@@ -89,3 +89,27 @@ def element_set():
     c5[0, 0] = 1
     return {"rect3": rect(3), "rect5": rect(5), "rect7": rect(7), "cross3": cross(3), "cross5": cross(5),
             "rect3x5": rect(3, 5), "random7": r7, "corner5": c5}
+
+
+OBLONG_SIDES = [(1, 3), (1, 7), (7, 1), (5, 1), (7, 3), (3, 7), (5, 3), (1, 1)]  # kh x kw
+
+
+def oblong_set():
+    """Elements that are not square, most of them wider than tall, as name "khxkw" -> element:
+    random members (1x7 and 7x1 without their centre, and not symmetric), so a flip, a transpose or
+    an element put off-centre into the square the GPU kernel is compiled for cannot pass."""
+    out = {}
+    for kh, kw in OBLONG_SIDES:
+        e = (np.random.default_rng([18, kh, kw]).integers(0, 2, (kh, kw)) != 0).astype(np.uint8)
+        if (kh, kw) in ((1, 7), (7, 1), (3, 7)):
+            e[kh // 2, kw // 2] = 0
+            e.flat[0], e.flat[-1] = 1, 0
+        if kh * kw > 1 and e.sum() < 2:  # more than the identity
+            e.flat[0] = 1
+        if not e.any():
+            e[kh // 2, kw // 2] = 1
+        out["%dx%d" % (kh, kw)] = e
+    for name in ("1x7", "7x1", "3x7"):
+        assert not out[name][out[name].shape[0] // 2, out[name].shape[1] // 2]
+        assert not np.array_equal(out[name], out[name][::-1, ::-1])
+    return out

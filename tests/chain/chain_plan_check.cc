@@ -6,6 +6,12 @@
 //              source, the result buffer reported, the count within live values + 1
 //   grid       a scalar model of each step run band by band (vf_conv_bands.h with ry = R), reading
 //              only rows the plan says exist, borders in frame coordinates, equals the whole frame
+//   random     seeded programs over the whole step space (oblong sides, a border per step, a == b,
+//              shared tables): validate accepts, fold keeps the picture, the schedule holds, and an
+//              executor that stores values in the plan's buffers at the band's row origin, in place
+//              where the plan says so, equals the whole frame for every capacity from 2 R + 1 rows up
+//   plan       the reach, the folded steps and the buffers of serialised programs, for the tests that
+//              compare them with tests/_chain_ref.py and name features of tests/_chain_gen.py's set
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -254,6 +260,45 @@ int run_fold() {
 
 // ---- buffers ----------------------------------------------------------------------------------------
 
+// The schedule of one program simulated: no live value overwritten, no neighbourhood step writes its
+// source, the result buffer reported, the count within live values + 1.
+void check_schedule(const Program &p, int *max_count, int *in_place) {
+  const int n = p.size();
+  const Buffers b = assign_buffers(p);
+  CHECK((int)b.of.size() == n + 1 && b.of[0] == 0 && b.result == b.of[n]);
+  std::vector<int> last(n + 1, 0);
+  for (int i = 1; i <= n; ++i) {
+    last[p.steps[i - 1].a] = i;
+    if (p.steps[i - 1].kind == kBinary) last[p.steps[i - 1].b] = i;
+  }
+  last[n] = n + 1;
+  std::vector<int> holds(b.count, -1);  // the value each buffer holds
+  holds[0] = 0;
+  int max_live = 1;
+  for (int i = 1; i <= n; ++i) {
+    const Step &s = p.steps[i - 1];
+    const int k = b.of[i];
+    CHECK(k >= 0 && k < b.count);
+    if (k < 0 || k >= b.count) break;
+    // the operands are where the plan says, not overwritten since
+    CHECK(holds[b.of[s.a]] == s.a);
+    if (s.kind == kBinary) CHECK(holds[b.of[s.b]] == s.b);
+    if (is_neighbourhood(s)) CHECK(k != b.of[s.a]);  // never writes the buffer it reads
+    const int u = holds[k];
+    if (u >= 0 && last[u] >= i) {  // overwrites a value some step from i on reads: only in place
+      CHECK(last[u] == i && !is_neighbourhood(s) && reads(s, u));
+      ++*in_place;
+    }
+    holds[k] = i;
+    int live = 1;  // value i and every earlier value still to be read (by step i too)
+    for (int v = 0; v < i; ++v) live += last[v] >= i;
+    if (live > max_live) max_live = live;
+  }
+  CHECK(holds[b.result] == n);
+  CHECK(b.count <= max_live + 1);
+  if (b.count > *max_count) *max_count = b.count;
+}
+
 int run_buffers() {
   const int B = vf::conv::kConstant;
   Program same;
@@ -266,40 +311,7 @@ int run_buffers() {
   int programs = 0, max_count = 0, in_place = 0;
   for (const Program &p : ps) {
     ++programs;
-    const int n = p.size();
-    const Buffers b = assign_buffers(p);
-    CHECK((int)b.of.size() == n + 1 && b.of[0] == 0 && b.result == b.of[n]);
-    std::vector<int> last(n + 1, 0);
-    for (int i = 1; i <= n; ++i) {
-      last[p.steps[i - 1].a] = i;
-      if (p.steps[i - 1].kind == kBinary) last[p.steps[i - 1].b] = i;
-    }
-    last[n] = n + 1;
-    std::vector<int> holds(b.count, -1);  // the value each buffer holds
-    holds[0] = 0;
-    int max_live = 1;
-    for (int i = 1; i <= n; ++i) {
-      const Step &s = p.steps[i - 1];
-      const int k = b.of[i];
-      CHECK(k >= 0 && k < b.count);
-      if (k < 0 || k >= b.count) break;
-      // the operands are where the plan says, not overwritten since
-      CHECK(holds[b.of[s.a]] == s.a);
-      if (s.kind == kBinary) CHECK(holds[b.of[s.b]] == s.b);
-      if (is_neighbourhood(s)) CHECK(k != b.of[s.a]);  // never writes the buffer it reads
-      const int u = holds[k];
-      if (u >= 0 && last[u] >= i) {  // overwrites a value some step from i on reads: only in place
-        CHECK(last[u] == i && !is_neighbourhood(s) && reads(s, u));
-        ++in_place;
-      }
-      holds[k] = i;
-      int live = 1;  // value i and every earlier value still to be read (by step i too)
-      for (int v = 0; v < i; ++v) live += last[v] >= i;
-      if (live > max_live) max_live = live;
-    }
-    CHECK(holds[b.result] == n);
-    CHECK(b.count <= max_live + 1);
-    if (b.count > max_count) max_count = b.count;
+    check_schedule(p, &max_count, &in_place);
   }
   CHECK(assign_buffers(blackhat3_it2(B)).count <= 3 && assign_buffers(edges(B)).count <= 3);
   CHECK(assign_buffers(diamond(B)).count == 2 && assign_buffers(fold(pointwise())).count == 1);
@@ -455,6 +467,281 @@ int run_rows(const char *name, int H, int y0, int y1) {
   return 0;
 }
 
+// ---- random: seeded programs through validate, fold, the schedule and a buffer-addressed executor ----
+
+struct Lcg {
+  unsigned s;
+  unsigned next() { return (s = s * 1664525u + 1013904223u) >> 8; }
+  int below(int n) { return (int)(next() % (unsigned)n); }  // 0 .. n - 1
+  bool chance(int percent) { return below(100) < percent; }
+};
+
+// A valid program of 1 .. 8 steps over the whole step space: permutation tables of 1 or (for
+// 3-channel frames) 3 channels, kernels and elements with independent odd sides 1 .. 7 and their own
+// border, the medians, all five binary ops with a == b for add / min / max.  The operands are steered
+// so that every value but the last is read: a step must read `must` values nobody has read yet when
+// the steps after it (one unread value fewer each, at best) could not read them all.
+Program random_program(Lcg &g, int channels) {
+  const int n = 1 + g.below(kMaxSteps);
+  Program p;
+  std::vector<int> unread{0};
+  auto take = [&](int v) {
+    for (size_t k = 0; k < unread.size(); ++k)
+      if (unread[k] == v) return (void)unread.erase(unread.begin() + (long)k);
+  };
+  for (int i = 1; i <= n; ++i) {
+    const int rem = n - i;
+    const int must = (int)unread.size() > rem ? (int)unread.size() - rem : 0;
+    auto operand = [&](int avoid) {
+      std::vector<int> fresh;
+      for (int v : unread)
+        if (v != avoid) fresh.push_back(v);
+      if (!fresh.empty() && (must || g.chance(70))) return fresh[(size_t)g.below((int)fresh.size())];
+      return g.below(i);
+    };
+    const int kind = must == 2 ? kBinary : g.below(4);
+    Step s;
+    s.kind = kind;
+    s.a = operand(-1);
+    if (kind == kTable) {
+      s.channels = channels == 3 && g.chance(50) ? 3 : 1;
+      s.table.resize((size_t)s.channels * 256);
+      for (int c = 0; c < s.channels; ++c) {  // a permutation: Fisher-Yates
+        uint8_t *t = s.table.data() + 256 * c;
+        for (int v = 0; v < 256; ++v) t[v] = (uint8_t)v;
+        for (int v = 255; v > 0; --v) std::swap(t[v], t[g.below(v + 1)]);
+      }
+    } else if (kind == kConv) {
+      s.kh = 1 + 2 * g.below(4), s.kw = 1 + 2 * g.below(4), s.border = g.below(3), s.shift = g.below(9);
+      const int m = g.chance(25) ? 8 + g.below(33) : 1 + g.below(3);
+      int sum = 0;
+      for (int k = 0; k < s.kw * s.kh; ++k) s.weights.push_back((int16_t)(g.below(2 * m + 1) - m)), sum += s.weights.back();
+      int16_t &centre = s.weights[(size_t)(s.kh / 2) * s.kw + s.kw / 2];
+      centre = (int16_t)(centre + (1 << s.shift) - sum);  // unit gain
+    } else if (kind == kRank) {
+      if (g.chance(25)) {
+        s.op = kMedian, s.kw = s.kh = g.chance(50) ? 3 : 5, s.border = vf::conv::kReplicate;
+        s.element.assign((size_t)s.kw * s.kh, 1);
+      } else {
+        s.op = g.below(2), s.kh = 1 + 2 * g.below(4), s.kw = 1 + 2 * g.below(4), s.border = g.below(3);
+        bool any = false;
+        for (int k = 0; k < s.kw * s.kh; ++k) s.element.push_back((uint8_t)g.below(2)), any |= s.element.back() != 0;
+        if (!any) s.element[(size_t)g.below(s.kw * s.kh)] = 1;
+      }
+    } else {
+      if (must < 2 && (i == 1 || g.chance(30))) {
+        const int same[3] = {kAdd, kMin, kMax};
+        s.op = same[g.below(3)], s.b = s.a;
+      } else {
+        s.op = g.below(5);
+        s.b = operand(s.a);
+        while (s.b == s.a) s.b = g.below(i);
+        if (g.chance(50)) std::swap(s.a, s.b);
+      }
+    }
+    take(s.a);
+    if (kind == kBinary) take(s.b);
+    unread.push_back(i);
+    p.steps.push_back(std::move(s));
+  }
+  return p;
+}
+
+int g_in_place_run = 0;
+
+// Rows [b.y0, b.y1) of the (folded) program's result, values stored the way vf_chain_frames_host
+// addresses them: one byte buffer per assign_buffers buffer, all of the band's source rows
+// [b.s0, b.s1); value v's row y at (y - b.s0) * row of its buffer; buffer 0 starts as the upload; a
+// table or binary step reads and writes byte by byte, in place where the plan gives it its
+// operand's buffer; a neighbourhood step gets its operand's first present row as its source, that
+// row's number and the count, and resolves a tap in frame coordinates before moving it into that
+// window; the last step writes the output rows.  tag[k][row] is the value a buffer row holds: a
+// read of a row that does not hold the operand, or an address outside a buffer, is a bad read.
+std::vector<uint8_t> run_band_buffers(const Program &p, const Frame &f, const std::vector<uint8_t> &img,
+                                      const vf::conv::Band &b) {
+  const int n = p.size();
+  const Buffers bufs = assign_buffers(p);
+  const std::vector<Rows> need = rows_needed(p, f.H, b.y0, b.y1);
+  const size_t row = f.row();
+  const int nsrc_rows = b.s1 - b.s0;
+  std::vector<std::vector<uint8_t>> buf((size_t)bufs.count, std::vector<uint8_t>((size_t)nsrc_rows * row, 0x5A));
+  std::vector<std::vector<int>> tag((size_t)bufs.count, std::vector<int>((size_t)nsrc_rows, -1));
+  std::memcpy(buf[0].data(), img.data() + (size_t)b.s0 * row, (size_t)nsrc_rows * row);
+  for (int &t : tag[0]) t = 0;
+  std::vector<uint8_t> out((size_t)(b.y1 - b.y0) * row, 0xA5);
+  // byte `off` of value v's row y, as at(v, y)[off] addresses it
+  auto load = [&](int v, int y, size_t off) -> uint8_t {
+    const int k = bufs.of[v], r = y - b.s0;
+    if (r < 0 || r >= nsrc_rows || tag[(size_t)k][(size_t)r] != v) {
+      ++g_bad_reads;
+      return 0x5A;
+    }
+    return buf[(size_t)k][(size_t)r * row + off];
+  };
+  for (int i = 1; i <= n; ++i) {
+    const Step &s = p.steps[i - 1];
+    const Rows r = need[i], ra = need[s.a];
+    const int k = bufs.of[i];
+    CHECK(r.lo >= b.s0 && r.hi <= b.s1 && r.lo < r.hi);
+    if (r.lo < b.s0 || r.hi > b.s1) return out;
+    if (i < n && (k == bufs.of[s.a] || (s.kind == kBinary && k == bufs.of[s.b]))) {
+      CHECK(!is_neighbourhood(s));
+      ++g_in_place_run;
+    }
+    for (int y = r.lo; y < r.hi; ++y) {
+      for (size_t off = 0; off < row; ++off) {
+        const int x = (int)(off / (size_t)f.C), c = (int)(off % (size_t)f.C);
+        int q = 0;
+        if (s.kind == kTable) {
+          q = through(s, c, load(s.a, y, off));
+        } else if (s.kind == kBinary) {
+          const int a = load(s.a, y, off), bb = load(s.b, y, off);
+          q = s.op == kSubtract ? a - bb : s.op == kAdd ? a + bb : s.op == kAbsdiff ? std::abs(a - bb) : s.op == kMin ? (a < bb ? a : bb) : (a > bb ? a : bb);
+        } else {
+          const int src_s0 = ra.lo, src_n = ra.hi - ra.lo;  // launch_conv / launch_rank's s0 and nsrc
+          int acc = 0, mn = 255, mx = 0, cnt = 0;
+          int med[49];
+          for (int j = 0; j < s.kh; ++j)
+            for (int t = 0; t < s.kw; ++t) {
+              if (s.kind == kRank && !s.element[(size_t)j * s.kw + t]) continue;
+              const int by = vf::conv::border_index(y + j - s.kh / 2, f.H, s.border);
+              const int bx = vf::conv::border_index(x + t - s.kw / 2, f.W, s.border);
+              if (by < 0 || bx < 0) continue;
+              const int sr = by - src_s0;
+              int v = 0x5A;
+              if (sr < 0 || sr >= src_n) ++g_bad_reads;  // the kernel would stage a neutral value here
+              else v = load(s.a, src_s0 + sr, (size_t)bx * f.C + c);
+              acc += s.kind == kConv ? v * s.weights[(size_t)j * s.kw + t] : 0;
+              mn = v < mn ? v : mn, mx = v > mx ? v : mx;
+              med[cnt++] = v;
+            }
+          if (s.kind == kConv) q = round_shift(acc, s.shift);
+          else if (s.op == kErode) q = mn;
+          else if (s.op == kDilate) q = mx;
+          else {
+            for (int a = 1; a < cnt; ++a)
+              for (int bb = a; bb > 0 && med[bb - 1] > med[bb]; --bb) std::swap(med[bb - 1], med[bb]);
+            q = med[cnt / 2];
+          }
+        }
+        const uint8_t byte = (uint8_t)(q < 0 ? 0 : q > 255 ? 255 : q);
+        if (i == n) out[(size_t)(y - r.lo) * row + off] = byte;
+        else buf[(size_t)k][(size_t)(y - b.s0) * row + off] = byte;
+      }
+      if (i < n) tag[(size_t)k][(size_t)(y - b.s0)] = i;
+    }
+  }
+  return out;
+}
+
+bool has_table3(const Program &p) {
+  for (const Step &s : p.steps)
+    if (s.kind == kTable && s.channels == 3) return true;
+  return false;
+}
+
+int run_random(int count) {
+  Lcg g{20240607u};
+  int programs = 0, cases = 0, multi_band = 0, bands_run = 0, folded = 0, max_count = 0, in_place = 0, max_reach = 0;
+  int oblong = 0, one_row = 0;
+  for (int k = 0; k < count; ++k) {
+    const int channels = k & 1 ? 3 : 1;
+    const Program p = random_program(g, channels);
+    ++programs;
+    std::string why;
+    const bool valid = validate(p, channels, &why);
+    if (!valid) std::fprintf(stderr, "program %d refused: %s\n", k, why.c_str());
+    CHECK(valid);
+    if (!valid) continue;
+    const Program fp = fold(p);
+    CHECK(validate(fp, channels, &why));
+    folded += fp.size() < p.size();
+    check_schedule(p, &max_count, &in_place);
+    check_schedule(fp, &max_count, &in_place);
+    const int R = reach(fp);
+    CHECK(R == reach(p));  // a table has no radius: folding moves no row
+    if (R > max_reach) max_reach = R;
+    for (const Step &s : p.steps) oblong += is_neighbourhood(s) && s.kw != s.kh, one_row += is_neighbourhood(s) && s.kh == 1 && s.kw > 1;
+    for (int H : {1, 2, 9, 40})
+      for (int W : {1, 5})
+        for (int C : {1, 3}) {
+          if (C == 1 && has_table3(p)) continue;
+          const Frame f{W, H, C};
+          std::vector<uint8_t> img((size_t)H * f.row());
+          for (uint8_t &b : img) b = (uint8_t)(g.next() >> 8);
+          // the whole frame by the scalar model of the program as written, every value its own vector
+          const Val whole = run_band(p, f, img, 0, H, 0, H);
+          const Val whole_folded = run_band(fp, f, img, 0, H, 0, H);
+          CHECK(whole.d == whole_folded.d);
+          const int need_rows = 2 * R + 1 < H ? 2 * R + 1 : H;
+          for (int rows = need_rows; rows <= H + 1; ++rows) {
+            std::vector<vf::conv::Band> bs;
+            ++cases;
+            const bool cut = vf::conv::bands(W, H, C, R, (size_t)rows * f.row(), &bs);
+            CHECK(cut);
+            if (!cut) continue;
+            multi_band += bs.size() > 1;
+            int next = 0;
+            for (const vf::conv::Band &b : bs) {
+              CHECK(b.y0 == next && b.y1 > b.y0 && b.s1 - b.s0 <= rows);
+              next = b.y1;
+              const std::vector<uint8_t> got = run_band_buffers(fp, f, img, b);
+              ++bands_run;
+              const bool same = std::memcmp(got.data(), whole.d.data() + (size_t)b.y0 * f.row(), got.size()) == 0;
+              if (!same && g_failed < 20)
+                std::fprintf(stderr, "program %d, %d x %d x %d, %d rows fit: rows [%d, %d) from [%d, %d) differ\n", k, W, H, C,
+                             rows, b.y0, b.y1, b.s0, b.s1);
+              CHECK(same);
+            }
+            CHECK(next == H);
+          }
+        }
+  }
+  CHECK(g_bad_reads == 0);
+  std::printf("{\"programs\": %d, \"cases\": %d, \"multi_band\": %d, \"bands\": %d, \"folded\": %d, \"max_count\": %d, "
+              "\"in_place\": %d, \"in_place_run\": %d, \"max_reach\": %d, \"oblong\": %d, \"one_row\": %d, \"bad_reads\": %d, "
+              "\"failed\": %d}\n",
+              programs, cases, multi_band, bands_run, folded, max_count, in_place, g_in_place_run, max_reach, oblong, one_row,
+              g_bad_reads, g_failed);
+  return g_failed ? 1 : 0;
+}
+
+// plan FILE: the plan of each serialised program (tests/_chain_gen.py's serialise: the structure,
+// no contents): its reach, the folded program's steps as [kind, a, b, op], its buffers and the result's.
+int run_plan(const char *path) {
+  std::FILE *fp = std::fopen(path, "r");
+  if (!fp) return 2;
+  std::printf("[");
+  int n = 0, channels = 0, count = 0;
+  char tagc = 0;
+  while (std::fscanf(fp, " %c %d %d", &tagc, &n, &channels) == 3 && tagc == 'P') {
+    Program p;
+    for (int i = 0; i < n; ++i) {
+      Step s;
+      int tch = 1;
+      if (std::fscanf(fp, "%d %d %d %d %d %d %d", &s.kind, &s.a, &s.b, &s.op, &s.kw, &s.kh, &tch) != 7) return std::fclose(fp), 2;
+      if (s.kind == kTable) s.channels = tch, s.table.assign((size_t)(tch == 3 ? 3 : 1) * 256, 0);
+      if (s.kind == kConv && s.kw > 0 && s.kh > 0) s.weights.assign((size_t)s.kw * s.kh, 1);
+      if (s.kind == kRank && s.kw > 0 && s.kh > 0) s.element.assign((size_t)s.kw * s.kh, 1);
+      p.steps.push_back(std::move(s));
+    }
+    std::string why;
+    const bool valid = validate(p, channels, &why);
+    const Program f = valid ? fold(p) : p;
+    const Buffers b = valid ? assign_buffers(f) : Buffers();
+    std::printf("%s{\"valid\": %s, \"reach\": %d, \"steps\": [", count++ ? ", " : "", valid ? "true" : "false", valid ? reach(p) : -1);
+    for (int i = 0; valid && i < f.size(); ++i)
+      std::printf("%s[%d, %d, %d, %d]", i ? ", " : "", f.steps[i].kind, f.steps[i].a,
+                  f.steps[i].kind == kBinary ? f.steps[i].b : -1, f.steps[i].op);
+    std::printf("], \"of\": [");
+    for (size_t v = 0; v < b.of.size(); ++v) std::printf("%s%d", v ? ", " : "", b.of[v]);
+    std::printf("], \"count\": %d, \"result\": %d}", b.count, b.result);
+  }
+  std::fclose(fp);
+  std::printf("]\n");
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -464,6 +751,8 @@ int main(int argc, char **argv) {
   if (mode == "buffers") return run_buffers();
   if (mode == "grid") return run_grid();
   if (mode == "rows" && argc == 6) return run_rows(argv[2], std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]));
-  std::fprintf(stderr, "usage: chain_plan_check validate | fold | buffers | grid | rows PROGRAM H y0 y1\n");
+  if (mode == "random") return run_random(argc > 2 ? std::atoi(argv[2]) : 500);
+  if (mode == "plan" && argc == 3) return run_plan(argv[2]);
+  std::fprintf(stderr, "usage: chain_plan_check validate | fold | buffers | grid | rows PROGRAM H y0 y1 | random [N] | plan FILE\n");
   return 2;
 }

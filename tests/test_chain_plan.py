@@ -8,6 +8,14 @@ It checks that each invalid program is refused with its reason; that a composed 
 tables in sequence; the buffer schedule by simulation; and that a scalar model of every step, run
 band by band on only the rows the plan says exist and with borders resolved in frame coordinates,
 equals the whole-frame result, for the programs ``edges``, ``blackhat3_it2`` and ``diamond``.
+
+Its ``random`` mode draws 500 seeded programs over the whole step space (``tests/_chain_gen.py``'s:
+oblong kernels and elements, a border per step, ``a == b``, shared tables) and runs the buffer
+schedule and the row plan together: an executor that keeps one byte buffer per planned buffer, puts
+value ``v``'s row ``y`` at ``(y - band.s0) * row`` as ``vf_chain_frames_host`` does, and runs table
+and binary steps in place where the plan says so.  Its ``plan`` mode prints the plan of the programs
+of ``tests/_chain_gen.py``, so that the reach of ``tests/_chain_ref.py`` and the features that need
+the plan (folding, buffers) are checked against the library's own text.
 """
 import json
 import os
@@ -15,6 +23,9 @@ import shutil
 import subprocess
 
 import pytest
+
+import _chain_gen as G
+import _chain_ref as CR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "distributed-video-filter_amd", "csrc")
@@ -34,7 +45,7 @@ def checker(tmp_path_factory):
 
 
 def _run(exe, *args):
-    p = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=120)
+    p = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, (args, p.returncode, p.stdout[-2000:], p.stderr[-4000:])
     return json.loads(p.stdout)
 
@@ -69,3 +80,66 @@ def test_the_rows_of_the_documented_bands(checker):
         "reach": 4, "rows": [[0, 341], [0, 340], [0, 339], [0, 338], [0, 337], [0, 337]]}
     # value 0 is read with reach 3 and with reach 0: the union; at the frame's end the rows are clipped
     assert _run(checker, "rows", "diamond", 40, 30, 40) == {"reach": 3, "rows": [[27, 40], [30, 40], [30, 40]]}
+
+
+def test_random_programs_through_the_schedule_and_the_row_plan_together(checker):
+    out = _run(checker, "random")
+    assert out["failed"] == 0 and out["bad_reads"] == 0, out
+    assert out["programs"] >= 500 and out["multi_band"] > 0 and out["in_place"] > 0 and out["in_place_run"] > 0, out
+    assert out["folded"] > 0 and out["oblong"] > 0 and out["one_row"] > 0 and out["max_reach"] >= 9, out
+
+
+@pytest.fixture(scope="module")
+def plans(checker, tmp_path_factory):
+    """name -> the plan of each program of tests/_chain_gen.py's two sets, by channels."""
+    out = {}
+    for channels, progs in ((3, G.PROGRAMS), (1, G.PROGRAMS_1)):
+        path = tmp_path_factory.mktemp("plan") / ("programs_%d.txt" % channels)
+        path.write_text(G.serialise(progs.values(), channels))
+        out[channels] = dict(zip(progs, _run(checker, "plan", path)))
+        assert len(out[channels]) == len(progs)
+    return out
+
+
+def test_the_generated_programs_are_valid_and_the_reference_reach_is_the_plans(plans):
+    for channels, progs in ((3, G.PROGRAMS), (1, G.PROGRAMS_1)):
+        for name, prog in progs.items():
+            plan = plans[channels][name]
+            assert plan["valid"], (channels, name)
+            assert plan["reach"] == CR.reach(prog), (channels, name)
+
+
+def test_the_generated_set_holds_the_features_that_need_the_plan(plans):
+    """Per channel count at least one program: whose tables fold; that keeps a table for its two
+    readers; whose result lands in buffer 0; with a subtract that runs in place over ``b`` while
+    ``a`` is read later; with ``a == b`` in place; that needs four buffers."""
+    K_TABLE, K_BINARY, SUBTRACT = 0, 3, 0
+    for channels, progs in ((3, G.PROGRAMS), (1, G.PROGRAMS_1)):
+        held = set()
+        for name, prog in progs.items():
+            plan = plans[channels][name]
+            steps, of = plan["steps"], plan["of"]  # the folded program
+            n = len(steps)
+            last = [0] * (n + 1)
+            readers = [0] * (n + 1)
+            for i, (kind, a, b, _) in enumerate(steps, 1):
+                for v in {a, b} if kind == K_BINARY else {a}:
+                    last[v] = i
+                    readers[v] += 1
+            if n < len(prog):
+                held.add("folded")
+            if any(kind == K_TABLE and readers[i] >= 2 for i, (kind, _, _, _) in enumerate(steps, 1)):
+                held.add("a table kept for its two readers")
+            if plan["result"] == 0:
+                held.add("the result in buffer 0")
+            for i, (kind, a, b, op) in enumerate(steps[:-1], 1):  # the last step writes the output rows
+                if kind == K_BINARY and op == SUBTRACT and a != b and of[i] == of[b] and last[a] > i:
+                    held.add("subtract in place over b while a lives")
+                if kind == K_BINARY and a == b and of[i] == of[a]:
+                    held.add("a == b in place")
+            if plan["count"] >= 4:
+                held.add("four buffers")
+        assert held == {"folded", "a table kept for its two readers", "the result in buffer 0",
+                        "subtract in place over b while a lives", "a == b in place", "four buffers"}, (channels, held)
+
+

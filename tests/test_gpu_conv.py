@@ -263,3 +263,101 @@ def test_errors_leave_the_context_usable(vf_ctx):
     finally:
         vf_ctx.free_device(d)
     still_works()
+
+
+# ---- kernels that are not square ------------------------------------------------------------------
+# The GPU kernel is compiled for the 3, 5 or 7 square that holds the kernel: a 1 x 7 kernel runs as
+# 7 x 7 with six rows of zero weights, and stages R = 3 halo rows that a band of vertical radius 0
+# does not hold.
+
+OBLONG = R.oblong_set()
+
+
+def _first_bad_row(got, want):
+    """Where two frames differ, by row: for messages."""
+    rows = np.flatnonzero((got != want).reshape(got.shape[0], -1).any(axis=1))
+    return "equal" if rows.size == 0 else "%d rows differ, the first is row %d, the last row %d" % (rows.size, rows[0], rows[-1])
+
+
+@pytest.mark.parametrize("border", BORDERS)
+@pytest.mark.parametrize("name", list(OBLONG))
+def test_oblong_kernels_on_straddling_shapes(vf_ctx, name, border):
+    k, s = OBLONG[name]
+    for c in (1, 3):
+        for w, h in STRADDLE:
+            img = _img(h, w, c)
+            got = vfilter.filter2d(img, (k, s), border=border, ctx=vf_ctx)
+            want = R.filter2d(img, k, s, border)
+            assert np.array_equal(got, want), (name, border, img.shape, np.argwhere(got != want)[:5])
+
+
+@pytest.mark.parametrize("name", ["1x7", "7x1"])
+@pytest.mark.parametrize("w,c", [(27, 3), (7, 3), (5, 3), (21, 1), (15, 1), (95, 1)])  # W * C mod 16 = 1, 5, 15
+@pytest.mark.parametrize("so,do", [(0, 0), (3, 3), (1, 5)])
+def test_oblong_kernels_off_the_16_byte_grid(vf_ctx, name, w, c, so, do):
+    h = TH + 3
+    img = _img(h, w, c)
+    n = img.nbytes
+    wts, s = vfilter.as_kernel(OBLONG[name])
+    got = np.empty(n + 64, np.uint8)
+    dsrc, ddst = vf_ctx.alloc_device(n + 64), vf_ctx.alloc_device(n + 64)
+    try:
+        vf_ctx.memset_device(ddst, 0xEE, n + 64)
+        vf_ctx.upload(dsrc + so, img, n)
+        vf_ctx.conv_device(dsrc + so, ddst + 16 + do, w, h, c, wts, s, 0)
+        vf_ctx.sync()
+        vf_ctx.download(got, ddst, n + 64)
+        vf_ctx.sync()
+    finally:
+        vf_ctx.free_device(dsrc)
+        vf_ctx.free_device(ddst)
+    lo = 16 + do
+    assert np.array_equal(got[lo:lo + n].reshape(img.shape), R.filter2d(img, *OBLONG[name]))
+    assert np.all(got[:lo] == 0xEE) and np.all(got[lo + n:] == 0xEE)  # the canaries on both sides
+
+
+@pytest.mark.parametrize("name", ["1x7", "7x1"])
+def test_bands_of_an_oblong_kernel(name):
+    """1024 x 700 x 3 in 1 MiB of staging, which holds 341 rows.  1 x 7 has ry = 0: the bands are rows
+    [0, 341), [341, 682), [682, 700) with no halo, and in place nothing is saved, yet the kernel
+    (compiled as 7 x 7) stages three rows above and below that the band does not hold.  7 x 1 has
+    ry = 3: bands [0, 338), [338, 673), [673, 700), each uploaded from three rows above."""
+    big = np.random.default_rng(11).integers(0, 256, (700, 1024, 3), dtype=np.uint8)
+    k, s = OBLONG[name]
+    wts, sh = vfilter.as_kernel((k, s))
+    with vfilter.Context(0, max_frame_bytes=1 << 20, max_batch=1) as ctx:
+        for border in ("reflect101", "constant"):
+            want = R.filter2d(big, k, s, border)
+            got = vfilter.filter2d(big, (k, s), border=border, ctx=ctx)
+            assert np.array_equal(got, want), (name, border, _first_bad_row(got, want))
+            buf = big.copy()  # host src is dst
+            ctx.conv_frames_host([buf], [buf], [1024], [700], 3, wts, sh, BORDERS.index(border))
+            assert np.array_equal(buf, want), (name, border, "in place", _first_bad_row(buf, want))
+
+
+@pytest.mark.parametrize("w,c", [(1, 3), (3, 1)])
+def test_the_row_seam_of_a_launch(vf_ctx, w, c):
+    """A launch is split at 65535 x 16 = 1,048,560 rows (the grid's y limit), each part with its own
+    first row and destination.  A frame of 1,048,577 rows of 3 bytes crosses the seam: the second
+    launch makes rows 1,048,560 to 1,048,576 and its taps reach back over the seam."""
+    h = 65535 * TH + 17
+    assert h == 1048577
+    img = np.random.default_rng([5, w, c]).integers(0, 256, (h, w, c) if c == 3 else (h, w), dtype=np.uint8)
+    n = img.nbytes
+    for name, pair in (("gaussian3", KERNELS["gaussian3"]), ("7x1", OBLONG["7x1"])):
+        want = R.filter2d(img, *pair)
+        wts, s = vfilter.as_kernel(pair)
+        got = np.empty_like(img)
+        dsrc, ddst = vf_ctx.alloc_device(n), vf_ctx.alloc_device(n)
+        try:
+            vf_ctx.upload(dsrc, img, n)
+            vf_ctx.conv_device(dsrc, ddst, w, h, c, wts, s, 0)
+            vf_ctx.sync()
+            vf_ctx.download(got, ddst, n)
+            vf_ctx.sync()
+        finally:
+            vf_ctx.free_device(dsrc)
+            vf_ctx.free_device(ddst)
+        assert np.array_equal(got, want), (name, "device", _first_bad_row(got, want))
+        got = vfilter.filter2d(img, pair, ctx=vf_ctx)
+        assert np.array_equal(got, want), (name, "host", _first_bad_row(got, want))
