@@ -86,8 +86,8 @@ struct vf_ctx {
   size_t raw_cap = 0;
   hipStream_t raw_stream = nullptr;
   uint8_t *raw_din = nullptr, *raw_dout = nullptr;
-  // vf_chain_frames_host's intermediate values: device buffers sized like raw_din, allocated by the
-  // first program that needs them (raw_mu held), freed with the context
+  // program_frames_host's intermediate values: device buffers sized like raw_din, allocated by the
+  // first program that needs them (raw_mu held; one of a single step needs none), freed with the context
   std::vector<uint8_t *> raw_scratch;
 };
 
@@ -497,6 +497,27 @@ int check_frame_shape(vf_ctx *ctx, const char *fn, int width, int height, int ch
   return VF_OK;
 }
 
+int check_channels(vf_ctx *ctx, const char *fn, int channels) {
+  if (channels != 1 && channels != 3)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: channels=%d, a frame has 1 or 3", fn, channels);
+  return VF_OK;
+}
+
+// The frame arguments vf_conv_device and vf_rank_device share; 1 for the empty frame: nothing to do.
+int check_device_frame(vf_ctx *ctx, const char *fn, const void *dsrc, const void *ddst, int width, int height,
+                       int channels) {
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if (width == 0 && height == 0) return 1;
+  if ((rc = check_frame_shape(ctx, fn, width, height, channels)) != VF_OK) return rc;
+  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL buffer", fn);
+  const size_t nbytes = (size_t)width * (size_t)channels * (size_t)height;
+  const uint8_t *s = (const uint8_t *)dsrc, *d = (const uint8_t *)ddst;
+  if (s < d + nbytes && d < s + nbytes)  // out of place only: a tap reads what a neighbour writes
+    return set_err(ctx, VF_E_INVALID, 0, "%s: src and dst overlap", fn);
+  return VF_OK;
+}
+
 }  // namespace
 
 VF_EXPORT int vf_conv_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
@@ -504,34 +525,69 @@ VF_EXPORT int vf_conv_device(vf_ctx *ctx, const void *dsrc, void *ddst, int widt
   VF_CHECK_CTX(ctx);
   int rc = check_kernel(ctx, "vf_conv_device", weights, kw, kh, shift, border);
   if (rc != VF_OK) return rc;
-  if (channels != 1 && channels != 3)
-    return set_err(ctx, VF_E_INVALID, 0, "vf_conv_device: channels=%d, a frame has 1 or 3", channels);
-  if (width == 0 && height == 0) return VF_OK;  // the empty frame
-  if ((rc = check_frame_shape(ctx, "vf_conv_device", width, height, channels)) != VF_OK) return rc;
-  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "vf_conv_device: NULL buffer");
-  const size_t nbytes = (size_t)width * (size_t)channels * (size_t)height;
-  const uint8_t *s = (const uint8_t *)dsrc, *d = (const uint8_t *)ddst;
-  if (s < d + nbytes && d < s + nbytes)  // out of place only: a tap reads what a neighbour writes
-    return set_err(ctx, VF_E_INVALID, 0, "vf_conv_device: src and dst overlap");
+  if ((rc = check_device_frame(ctx, "vf_conv_device", dsrc, ddst, width, height, channels)) != VF_OK)
+    return rc < 0 ? rc : VF_OK;
   VF_HIP(ctx, hipSetDevice(ctx->device));
   VF_HIP(ctx, vf::launch_conv(dsrc, ddst, width, channels, height, 0, height, 0, height, weights, kw, kh, shift, border,
                               vf::conv_form_env(), (hipStream_t)stream));
   return VF_OK;
 }
 
+// ---- programs: every chain, and a convolution or rank filter as a program of one step ------------
+
+// The one place that turns the steps of a program into kernel launches (declared in vf_internal.h):
+// it walks vf_chain_plan.h's band_launches and switches on the step's kind.  The raw host path
+// below and the JPEG path (vf_jpeg_host.hip) both come here; neither launches a step's kernel itself.
+namespace vf {
+
+hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const std::vector<chain::Launch> &launches,
+                        uint8_t *const *bufs, uint8_t *out, int w, int channels, int frame_h, int conv_form,
+                        const LaunchCfg &cfg, hipStream_t stream) {
+  const size_t row = (size_t)w * (size_t)channels;
+  for (const chain::Launch &l : launches) {
+    const chain::Step &s = prog.steps[(size_t)l.step - 1];
+    const uint8_t *a = bufs[l.a_buf] + (size_t)l.a_row * row;
+    uint8_t *dst = l.dst_buf == chain::kOut ? out : bufs[l.dst_buf] + (size_t)l.dst_row * row;
+    const size_t nbytes = (size_t)l.nrows * row;
+    hipError_t e;
+    if (s.kind == chain::kTable)
+      e = launch_lut(a, dst, nbytes, s.table.data(), s.channels, 0, cfg, stream);
+    else if (s.kind == chain::kBinary)
+      e = launch_binary(a, bufs[l.b_buf] + (size_t)l.b_row * row, dst, nbytes, s.op, cfg, stream);
+    else if (s.kind == chain::kConv)
+      e = launch_conv(a, dst, w, channels, frame_h, l.y0, l.nrows, l.src0, l.nsrc, s.weights.data(), s.kw, s.kh,
+                      s.shift, s.border, conv_form, stream);
+    else
+      e = launch_rank(a, dst, w, channels, frame_h, l.y0, l.nrows, l.src0, l.nsrc, s.op, masks[l.step - 1], s.kw, s.kh,
+                      s.border, stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace vf
+
 namespace {
 
-// The host path of the neighbourhood filters (vf_conv_frames_host, vf_rank_frames_host): the
-// frames' checks, the bands (vf_conv_bands.h) for a filter of vertical radius ry, and per fill of
-// the staging buffers upload, launch(din, dout, frame, band, stream), download, wait.
-template <class Launch>
-int neighbour_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs, uint8_t *const *dsts,
-                          const int *widths, const int *heights, int n, int channels, int ry, Launch &&launch) {
-  if (channels != 1 && channels != 3)
-    return set_err(ctx, VF_E_INVALID, 0, "%s: channels=%d, a frame has 1 or 3", fn, channels);
+int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps, int channels, vf::chain::Program *out,
+                  std::vector<uint64_t> *masks);  // below, with the chains
+
+// The host path of every program, a vf_step list: its checks and the frames', the bands
+// (vf_conv_bands.h) for the program's vertical reach, and per fill of the staging buffers upload,
+// the band's launches, download, wait.
+// One band: value v's row y sits at (its buffer) + (y - band.s0) * row, every buffer at the one row
+// origin, so an in-place step is dst == operand exactly.  Buffer 0 is the band's upload, the others
+// are the context's scratch (the pieces of one fill share it: they run in order on the one
+// stream); the last step writes the band's output rows straight into dout.
+int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs, uint8_t *const *dsts,
+                        const int *widths, const int *heights, int n, int channels, const vf_step *steps, int nsteps) {
+  vf::chain::Program prog;
+  std::vector<uint64_t> masks;
+  int rc = chain_program(ctx, fn, steps, nsteps, channels, &prog, &masks);
+  if (rc != VF_OK) return rc;
+  const int ry = vf::chain::reach(prog);
   if (n < 0) return set_err(ctx, VF_E_INVALID, 0, "%s: n < 0", fn);
   if (n > 0 && (!srcs || !dsts || !widths || !heights)) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL array", fn);
-  int rc;
   // one upload + launch + download per band (vf_conv_bands.h); most frames are one band
   struct Piece {
     int frame;
@@ -566,6 +622,15 @@ int neighbour_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *src
   VF_HIP(ctx, hipSetDevice(ctx->device));
   const size_t alloc = ((cap + 15 + 15) & ~(size_t)15);
   if ((rc = raw_staging(ctx, fn, alloc)) != VF_OK) return rc;
+  const vf::chain::Buffers bufs = vf::chain::assign_buffers(prog);
+  while ((int)ctx->raw_scratch.size() < vf::chain::scratch_buffers(bufs, prog, true)) {
+    void *p = nullptr;
+    VF_HIP(ctx, hipMalloc(&p, alloc));
+    ctx->raw_scratch.push_back(static_cast<uint8_t *>(p));
+  }
+  uint8_t *base[vf::chain::kMaxSteps + 1] = {};  // base[0]: each piece's upload; a value per step at the most
+  std::copy(ctx->raw_scratch.begin(), ctx->raw_scratch.end(), base + 1);
+  const int form = vf::conv_form_env();
   hipStream_t st = ctx->raw_stream;
   std::vector<size_t> at(pieces.size());
   for (size_t i = 0; i < pieces.size();) {
@@ -584,7 +649,10 @@ int neighbour_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *src
         VF_HIP(ctx, hipMemcpyAsync(din, p.halo, head, hipMemcpyHostToDevice, st));
       }
       VF_HIP(ctx, hipMemcpyAsync(din + head, src + (size_t)p.b.s0 * row + head, in_bytes - head, hipMemcpyHostToDevice, st));
-      VF_HIP(ctx, launch(din, dout, widths[p.frame], heights[p.frame], p.b, st));
+      base[0] = din;
+      const int w = widths[p.frame], h = heights[p.frame];
+      VF_HIP(ctx, vf::run_launches(prog, masks.data(), vf::chain::band_launches(prog, bufs, h, p.b.y0, p.b.y1, p.b.s0, true),
+                                   base, dout, w, channels, h, form, ctx->cfg, st));
       at[j] = cout;
       cin += (in_bytes + 15) & ~(size_t)15;
       cout += (out_bytes + 15) & ~(size_t)15;
@@ -610,12 +678,8 @@ VF_EXPORT int vf_conv_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
   const char *fn = "vf_conv_frames_host";
   const int rc = check_kernel(ctx, fn, weights, kw, kh, shift, border);
   if (rc != VF_OK) return rc;
-  const int form = vf::conv_form_env();
-  return neighbour_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, kh / 2,
-                               [&](const uint8_t *din, uint8_t *dout, int w, int h, const vf::conv::Band &b, hipStream_t st) {
-                                 return vf::launch_conv(din, dout, w, channels, h, b.y0, b.y1 - b.y0, b.s0, b.s1 - b.s0,
-                                                        weights, kw, kh, shift, border, form, st);
-                               });
+  const vf_step step{VF_STEP_CONV, 0, 0, 0, weights, kw, kh, shift, border, 0};  // a program of one step
+  return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
 }
 
 // ---- rank filters (cv2.erode, cv2.dilate, cv2.medianBlur) on raw frames ---------------------------
@@ -655,15 +719,8 @@ VF_EXPORT int vf_rank_device(vf_ctx *ctx, const void *dsrc, void *ddst, int widt
   uint64_t mask = 0;
   int rc = check_rank(ctx, "vf_rank_device", op, element, kw, kh, border, &mask);
   if (rc != VF_OK) return rc;
-  if (channels != 1 && channels != 3)
-    return set_err(ctx, VF_E_INVALID, 0, "vf_rank_device: channels=%d, a frame has 1 or 3", channels);
-  if (width == 0 && height == 0) return VF_OK;  // the empty frame
-  if ((rc = check_frame_shape(ctx, "vf_rank_device", width, height, channels)) != VF_OK) return rc;
-  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "vf_rank_device: NULL buffer");
-  const size_t nbytes = (size_t)width * (size_t)channels * (size_t)height;
-  const uint8_t *s = (const uint8_t *)dsrc, *d = (const uint8_t *)ddst;
-  if (s < d + nbytes && d < s + nbytes)  // out of place only: a tap reads what a neighbour writes
-    return set_err(ctx, VF_E_INVALID, 0, "vf_rank_device: src and dst overlap");
+  if ((rc = check_device_frame(ctx, "vf_rank_device", dsrc, ddst, width, height, channels)) != VF_OK)
+    return rc < 0 ? rc : VF_OK;
   VF_HIP(ctx, hipSetDevice(ctx->device));
   VF_HIP(ctx, vf::launch_rank(dsrc, ddst, width, channels, height, 0, height, 0, height, op, mask, kw, kh, border,
                               (hipStream_t)stream));
@@ -678,11 +735,8 @@ VF_EXPORT int vf_rank_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
   uint64_t mask = 0;
   const int rc = check_rank(ctx, fn, op, element, kw, kh, border, &mask);
   if (rc != VF_OK) return rc;
-  return neighbour_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, kh / 2,
-                               [&](const uint8_t *din, uint8_t *dout, int w, int h, const vf::conv::Band &b, hipStream_t st) {
-                                 return vf::launch_rank(din, dout, w, channels, h, b.y0, b.y1 - b.y0, b.s0, b.s1 - b.s0, op,
-                                                        mask, kw, kh, border, st);
-                               });
+  const vf_step step{VF_STEP_RANK, 0, 0, op, element, kw, kh, 0, border, 0};  // a program of one step
+  return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
 }
 
 // ---- filter chains: a program of table / conv / rank / binary steps on raw frames ------------------
@@ -693,13 +747,12 @@ namespace {
 // the structure (vf_chain_plan.h).  masks[i]: the element of step i + 1 of the FOLDED program.
 int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps, int channels, vf::chain::Program *out,
                   std::vector<uint64_t> *masks) {
-  if (channels != 1 && channels != 3)
-    return set_err(ctx, VF_E_INVALID, 0, "%s: channels=%d, a frame has 1 or 3", fn, channels);
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
   if (nsteps < 1 || nsteps > VF_CHAIN_MAX_STEPS)
     return set_err(ctx, VF_E_INVALID, 0, "%s: a program of %d steps; it has 1 to %d", fn, nsteps, VF_CHAIN_MAX_STEPS);
   if (!steps) return set_err(ctx, VF_E_INVALID, 0, "%s: steps is NULL", fn);
   vf::chain::Program p;
-  int rc;
   for (int i = 0; i < nsteps; ++i) {
     const vf_step &in = steps[i];
     vf::chain::Step s;
@@ -760,54 +813,7 @@ VF_EXPORT int vf_binary_device(vf_ctx *ctx, const void *da, const void *db, void
 VF_EXPORT int vf_chain_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
                                    const int *heights, int n, int channels, const vf_step *steps, int nsteps) {
   VF_CHECK_CTX(ctx);
-  const char *fn = "vf_chain_frames_host";
-  vf::chain::Program prog;
-  std::vector<uint64_t> masks;
-  const int rc = chain_program(ctx, fn, steps, nsteps, channels, &prog, &masks);
-  if (rc != VF_OK) return rc;
-  const vf::chain::Buffers bufs = vf::chain::assign_buffers(prog);
-  const int form = vf::conv_form_env();
-  const int nst = prog.size();
-  // One band: value v's row y sits at (its buffer) + (y - band.s0) * row, every buffer at the one
-  // row origin, so an in-place step is dst == operand exactly.  Buffer 0 is the band's upload, the
-  // others are the context's scratch (the pieces of one fill share it: they run in order on the
-  // one stream); the last step writes the band's output rows straight into dout.
-  return neighbour_frames_host(
-      ctx, fn, srcs, dsts, widths, heights, n, channels, vf::chain::reach(prog),
-      [&](uint8_t *din, uint8_t *dout, int w, int h, const vf::conv::Band &b, hipStream_t st) -> hipError_t {
-        const size_t alloc = ((ctx->raw_cap + 15 + 15) & ~(size_t)15);
-        while ((int)ctx->raw_scratch.size() + 1 < bufs.count) {
-          void *p = nullptr;
-          const hipError_t e = hipMalloc(&p, alloc);
-          if (e != hipSuccess) return e;
-          ctx->raw_scratch.push_back(static_cast<uint8_t *>(p));
-        }
-        const size_t row = (size_t)w * (size_t)channels;
-        const std::vector<vf::chain::Rows> need = vf::chain::rows_needed(prog, h, b.y0, b.y1);
-        auto at = [&](int v, int y) -> uint8_t * {
-          uint8_t *base = bufs.of[v] == 0 ? din : ctx->raw_scratch[bufs.of[v] - 1];
-          return base + (size_t)(y - b.s0) * row;
-        };
-        for (int i = 1; i <= nst; ++i) {
-          const vf::chain::Step &s = prog.steps[i - 1];
-          const vf::chain::Rows r = need[i], ra = need[s.a];
-          uint8_t *dst = i == nst ? dout : at(i, r.lo);
-          const size_t nbytes = (size_t)(r.hi - r.lo) * row;
-          hipError_t e;
-          if (s.kind == vf::chain::kTable)
-            e = vf::launch_lut(at(s.a, r.lo), dst, nbytes, s.table.data(), s.channels, 0, ctx->cfg, st);
-          else if (s.kind == vf::chain::kBinary)
-            e = vf::launch_binary(at(s.a, r.lo), at(s.b, r.lo), dst, nbytes, s.op, ctx->cfg, st);
-          else if (s.kind == vf::chain::kConv)
-            e = vf::launch_conv(at(s.a, ra.lo), dst, w, channels, h, r.lo, r.hi - r.lo, ra.lo, ra.hi - ra.lo,
-                                s.weights.data(), s.kw, s.kh, s.shift, s.border, form, st);
-          else
-            e = vf::launch_rank(at(s.a, ra.lo), dst, w, channels, h, r.lo, r.hi - r.lo, ra.lo, ra.hi - ra.lo, s.op,
-                                masks[i - 1], s.kw, s.kh, s.border, st);
-          if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-      });
+  return program_frames_host(ctx, "vf_chain_frames_host", srcs, dsts, widths, heights, n, channels, steps, nsteps);
 }
 
 // ---- memory helpers ------------------------------------------------------------------------
@@ -994,6 +1000,22 @@ VF_EXPORT int vf_bench_device_ring(vf_ctx *ctx, void *const *srcs, void *const *
 
 namespace {
 
+// A free codec, or a new one while the context has fewer than `most` (ctx->jpeg_mu held); nullptr
+// when neither, or out of host memory.
+vf::jpeg::Codec *take_codec(vf_ctx *ctx, size_t most) {
+  vf::jpeg::Codec *c = nullptr;
+  if (!ctx->jpeg_free.empty()) {
+    c = ctx->jpeg_free.back();
+    ctx->jpeg_free.pop_back();
+  } else if (ctx->jpeg_all.size() < most) {
+    static const bool gated = env_size("VF_JPEG_GATE", 0) != 0;
+    c = new (std::nothrow) vf::jpeg::Codec(ctx->device, gated ? &ctx->jpeg_gate : nullptr);
+    if (c) ctx->jpeg_all.push_back(c);
+  }
+  if (c) c->set_max_pixels(ctx->jpeg_max_pixels.load());
+  return c;
+}
+
 // A codec leased to one call for its duration (blocks while all codecs are busy).
 class CodecLease {
  public:
@@ -1001,15 +1023,7 @@ class CodecLease {
     static const size_t kMax = std::max<size_t>(1, env_size("VF_JPEG_CODECS", 2));
     std::unique_lock<std::mutex> lk(ctx->jpeg_mu);
     ctx->jpeg_cv.wait(lk, [&] { return !ctx->jpeg_free.empty() || ctx->jpeg_all.size() < kMax; });
-    if (!ctx->jpeg_free.empty()) {
-      c_ = ctx->jpeg_free.back();
-      ctx->jpeg_free.pop_back();
-    } else {
-      static const bool gated = env_size("VF_JPEG_GATE", 0) != 0;
-      c_ = new (std::nothrow) vf::jpeg::Codec(ctx->device, gated ? &ctx->jpeg_gate : nullptr);
-      if (c_) ctx->jpeg_all.push_back(c_);
-    }
-    if (c_) c_->set_max_pixels(ctx->jpeg_max_pixels.load());
+    c_ = take_codec(ctx, kMax);
   }
   ~CodecLease() {
     if (!c_) return;
@@ -1034,17 +1048,7 @@ class CodecLease {
 constexpr size_t kMaxJpegJobs = 8;
 vf::jpeg::Codec *lease_nowait(vf_ctx *ctx) {
   std::lock_guard<std::mutex> lk(ctx->jpeg_mu);
-  vf::jpeg::Codec *c = nullptr;
-  if (!ctx->jpeg_free.empty()) {
-    c = ctx->jpeg_free.back();
-    ctx->jpeg_free.pop_back();
-  } else if (ctx->jpeg_all.size() < kMaxJpegJobs) {
-    static const bool gated = env_size("VF_JPEG_GATE", 0) != 0;
-    c = new (std::nothrow) vf::jpeg::Codec(ctx->device, gated ? &ctx->jpeg_gate : nullptr);
-    if (c) ctx->jpeg_all.push_back(c);
-  }
-  if (c) c->set_max_pixels(ctx->jpeg_max_pixels.load());
-  return c;
+  return take_codec(ctx, kMaxJpegJobs);
 }
 
 void give_back(vf_ctx *ctx, vf::jpeg::Codec *c) {
@@ -1201,43 +1205,36 @@ int table_filter(vf_ctx *ctx, const char *fn, const uint8_t *table, int channels
   return VF_OK;
 }
 
+// A program as a batch's filter.  One that folds to a single table runs as that table, in the fused
+// colour stage; anything else is Filter::kChain, its plan built here once and shared by the codec's
+// copy.  The decoded frames have three channels.
+int chain_filter(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps, Filter *out) {
+  auto spec = std::make_shared<vf::jpeg::ChainSpec>();
+  const int rc = chain_program(ctx, fn, steps, nsteps, 3, &spec->prog, &spec->masks);
+  if (rc != VF_OK) return rc;
+  if (vf::chain::single_kind(spec->prog) == vf::chain::kTable)
+    return table_filter(ctx, fn, spec->prog.steps[0].table.data(), spec->prog.steps[0].channels, out);
+  spec->bufs = vf::chain::assign_buffers(spec->prog);
+  out->kind = Filter::kChain;
+  out->chain = std::move(spec);
+  return VF_OK;
+}
+
+// A convolution or a rank filter is a program of one step.
 int conv_filter(vf_ctx *ctx, const char *fn, const int16_t *weights, int kw, int kh, int shift, int border,
                 Filter *out) {
   const int rc = check_kernel(ctx, fn, weights, kw, kh, shift, border);
   if (rc != VF_OK) return rc;
-  out->kind = Filter::kConv;
-  out->conv = vf::jpeg::ConvSpec{{}, kw, kh, shift, border};
-  std::memcpy(out->conv.w, weights, sizeof(int16_t) * (size_t)(kw * kh));
-  return VF_OK;
+  const vf_step step{VF_STEP_CONV, 0, 0, 0, weights, kw, kh, shift, border, 0};
+  return chain_filter(ctx, fn, &step, 1, out);
 }
 
 int rank_filter(vf_ctx *ctx, const char *fn, int op, const uint8_t *element, int kw, int kh, int border, Filter *out) {
   uint64_t mask = 0;
   const int rc = check_rank(ctx, fn, op, element, kw, kh, border, &mask);
   if (rc != VF_OK) return rc;
-  out->kind = Filter::kRank;
-  out->rank = vf::jpeg::RankSpec{op, mask, kw, kh, border};
-  return VF_OK;
-}
-
-// A program as a batch's filter.  One that folds to a single table, convolution or rank step runs
-// as that kind (a table in the fused colour stage); anything else is Filter::kChain, its plan
-// built here once and shared by the codec's copy.  The decoded frames have three channels.
-int chain_filter(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps, Filter *out) {
-  auto spec = std::make_shared<vf::jpeg::ChainSpec>();
-  const int rc = chain_program(ctx, fn, steps, nsteps, 3, &spec->prog, &spec->masks);
-  if (rc != VF_OK) return rc;
-  const int one = vf::chain::single_kind(spec->prog);
-  if (one >= 0) {
-    const vf::chain::Step &s = spec->prog.steps[0];
-    if (one == vf::chain::kTable) return table_filter(ctx, fn, s.table.data(), s.channels, out);
-    if (one == vf::chain::kConv) return conv_filter(ctx, fn, s.weights.data(), s.kw, s.kh, s.shift, s.border, out);
-    return rank_filter(ctx, fn, s.op, s.element.data(), s.kw, s.kh, s.border, out);
-  }
-  spec->bufs = vf::chain::assign_buffers(spec->prog);
-  out->kind = Filter::kChain;
-  out->chain = std::move(spec);
-  return VF_OK;
+  const vf_step step{VF_STEP_RANK, 0, 0, op, element, kw, kh, 0, border, 0};
+  return chain_filter(ctx, fn, &step, 1, out);
 }
 
 }  // namespace

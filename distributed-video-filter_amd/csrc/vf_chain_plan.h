@@ -8,7 +8,9 @@
 //   * folding   a table step whose only reader is a table step is composed into that reader;
 //   * buffers   which buffer each value lives in, assigned by last use;
 //   * rows      working backwards from an output band, the rows of every value that must exist,
-//               and the program's total vertical reach R.
+//               and the program's total vertical reach R;
+//   * launches  per band, every step with its buffers, row offsets and row ranges: the list that
+//               both GPU paths walk and the CPU check simulates.
 // Every step sees whole-frame borders: a step that makes rows [lo, hi) of its value from an
 // operand of vertical radius r reads the operand's rows [lo - r, hi + r) clipped to the frame, and
 // resolves its border in FRAME coordinates (vf_conv_border.h) exactly as one band of
@@ -18,6 +20,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -240,6 +243,49 @@ inline int reach(const Program &p) {
     if (s.kind == kBinary && t > r[s.b]) r[s.b] = t;
   }
   return r[0] < 0 ? 0 : r[0];
+}
+
+// ---- launches ------------------------------------------------------------------------------------
+
+constexpr int kOut = -1;  // Launch::dst_buf: the caller's output rows, not a buffer
+
+// One step of one band, fully addressed for its kernel (run_launches, vf_api.hip).  Every
+// buffer holds its value's row y at row y - s0, s0 the band's origin row.
+struct Launch {
+  int step;                   // 1-based; prog.steps[step - 1]
+  int a_buf, b_buf;           // buffers of the operands (b_buf read by binary steps only)
+  int dst_buf;                // buffer of the result, or kOut
+  int a_row, b_row, dst_row;  // first row handed to the kernel, relative to s0
+  int y0, nrows;              // the rows of this value to make (frame coordinates)
+  int src0, nsrc;             // the operand's first row handed over and the count (launch_conv's s0, nsrc)
+};
+
+// The launches that make rows [y0, y1) of the result for a frame of H rows whose buffers start at
+// row s0 (the whole frame: y0 = 0, y1 = H, s0 = 0).  A table or binary step reads its operands at
+// its own first row; a neighbourhood step gets every present row of its operand.  With
+// result_to_out the last step writes row 0 of the caller's output, else its planned buffer.
+inline std::vector<Launch> band_launches(const Program &p, const Buffers &bufs, int H, int y0, int y1, int s0,
+                                         bool result_to_out) {
+  const int n = p.size();
+  const std::vector<Rows> need = rows_needed(p, H, y0, y1);
+  std::vector<Launch> out;
+  for (int i = 1; i <= n; ++i) {
+    const Step &s = p.steps[i - 1];
+    const Rows r = need[i], src = is_neighbourhood(s) ? need[s.a] : r;
+    const bool to_out = result_to_out && i == n;
+    out.push_back(Launch{i, bufs.of[s.a], bufs.of[s.kind == kBinary ? s.b : s.a], to_out ? kOut : bufs.of[i], src.lo - s0,
+                         r.lo - s0, to_out ? 0 : r.lo - s0, r.lo, r.hi - r.lo, src.lo, src.hi - src.lo});
+  }
+  return out;
+}
+
+// The buffers beyond buffer 0 that some launch addresses: bufs.count - 1 when the result stays in
+// its buffer, 0 for a one-step program whose result goes to the caller's output.
+inline int scratch_buffers(const Buffers &bufs, const Program &p, bool result_to_out) {
+  int top = 0;
+  for (const Launch &l : band_launches(p, bufs, 1, 0, 1, 0, result_to_out))
+    top = std::max({top, l.a_buf, l.b_buf, l.dst_buf});
+  return top;
 }
 
 }  // namespace chain

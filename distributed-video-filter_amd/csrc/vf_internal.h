@@ -68,6 +68,18 @@ hipError_t launch_rank(const void *dsrc, void *ddst, int width, int channels, in
 hipError_t launch_binary(const void *da, const void *db, void *ddst, size_t nbytes, int op, const LaunchCfg &cfg,
                          hipStream_t stream);
 
+// The steps of a program as launches of the four kernels above (vf_api.hip): `launches` is
+// vf_chain_plan.h's band_launches of a band or whole frame, masks[i] step i + 1's element when it
+// is a rank step, bufs[k] the address of buffer k's origin row (the band's row s0), out the rows a
+// chain::kOut launch writes; conv_form as launch_conv's form.
+namespace chain {
+struct Program;
+struct Launch;
+}  // namespace chain
+hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const std::vector<chain::Launch> &launches,
+                        uint8_t *const *bufs, uint8_t *out, int w, int channels, int frame_h, int conv_form,
+                        const LaunchCfg &cfg, hipStream_t stream);
+
 // Up to kMappedMax page-locked host ranges, by their device addresses, inverted in place over
 // PCIe by one launch (vf_kernels.hip invert_mapped_kernel; passed by value as kernel arguments).
 constexpr int kMappedMax = 64;

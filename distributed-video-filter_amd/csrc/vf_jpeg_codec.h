@@ -92,24 +92,10 @@ struct ComputeGate {
   hipEvent_t last = nullptr;
 };
 
-// The 2-D convolution filter of a batch (vf_jpeg_conv*): kw x kh integer weights, row-major, the
-// result shifted right by `shift` with round-half-even, `border` a VF_BORDER_* (DESIGN.md 16).
-struct ConvSpec {
-  int16_t w[49];
-  int kw, kh, shift, border;
-};
-
-// The rank filter of a batch (vf_jpeg_rank*): `op` a VF_RANK_*, `mask` the members of the kw x kh
-// element (bit j * kw + i), `border` a VF_BORDER_* (DESIGN.md 18).
-struct RankSpec {
-  int op;
-  uint64_t mask;
-  int kw, kh, border;
-};
-
-// The filter chain of a batch (vf_jpeg_chain*): the validated, folded program (vf_chain_plan.h), the
-// element masks of its rank steps and its buffer assignment.  Immutable once built; a
-// Filter shares it, so a Filter of the other kinds grows by one pointer and not by the program.
+// The program of a batch (vf_jpeg_chain*, and vf_jpeg_conv* / vf_jpeg_rank* as a program of one
+// step): validated and folded (vf_chain_plan.h), with the element masks of its rank steps and its
+// buffer assignment.  Immutable once built; a Filter shares it, so a Filter of the
+// other kinds grows by one pointer and not by the program.
 struct ChainSpec {
   chain::Program prog;
   std::vector<uint64_t> masks;  // masks[i]: step i + 1's element when it is a rank step
@@ -118,17 +104,16 @@ struct ChainSpec {
 
 // The filter of one batch of the invert path, as one value (vf_api.hip builds it from an entry point's
 // checked arguments); default-constructed, the inversion (cv2.bitwise_not).  The codec copies it, so
-// a batch resynchronised at wait_invert is filtered again by the same table, kernel or element.
+// a batch resynchronised at wait_invert is filtered again by the same table or program.
 struct Filter {
-  enum Kind { kNone, kInvert, kTable, kConv, kRank, kChain } kind = kInvert;  // kNone: the plain decode, pixels stay as decoded
-  LutTable lut = {};   // kTable: cv2.LUT on the decoded BGR pixels; a one-channel table is stored three times
-  ConvSpec conv = {};  // kConv: cv2.filter2D on them
-  RankSpec rank = {};  // kRank: cv2.erode / dilate / medianBlur on them
-  std::shared_ptr<const ChainSpec> chain;  // kChain: a program of those and the binary kernel, on them
+  enum Kind { kNone, kInvert, kTable, kChain } kind = kInvert;  // kNone: the plain decode, pixels stay as decoded
+  LutTable lut = {};  // kTable: cv2.LUT on the decoded BGR pixels; a one-channel table is stored three times
+  // kChain: a program of table, convolution, rank and binary steps on them; cv2.filter2D, cv2.erode,
+  // cv2.dilate and cv2.medianBlur are programs of one step
+  std::shared_ptr<const ChainSpec> chain;
   bool in_colour() const { return kind == kInvert || kind == kTable; }  // the colour stage filters
-  // a neighbourhood filter or a chain runs between decode (d_pix_) and encode (d_pix2_, or the
-  // buffer that holds a chain's result)
-  bool between() const { return kind == kConv || kind == kRank || kind == kChain; }
+  // a program runs between decode (d_pix_) and encode (the buffer that holds its result)
+  bool between() const { return kind == kChain; }
 };
 
 int header_info(const uint8_t *jpeg, size_t size, int *w, int *h, int *subsamp, int *colorspace, std::string *err);
@@ -187,7 +172,7 @@ class Codec {
                      bool fastdct, std::string *err);
   // pix: the BGR / RGB pixels the encoder reads when the plan is not fused (d_pix_ or d_pix2_)
   int run_encode(int bgr, bool fastdct, const uint8_t *pix, std::string *err);
-  // what the invert path queues behind its decode: the convolution, if the batch has one, and the encode
+  // what the invert path queues behind its decode: the program, if the batch has one, and the encode
   int run_filter_encode(bool fastdct, std::string *err);
   int queue_fetch(uint64_t guess, std::string *err);
   int finish_fetch(std::string *err);

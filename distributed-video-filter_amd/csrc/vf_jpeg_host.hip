@@ -872,61 +872,38 @@ int Codec::prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs
   return kOk;
 }
 
-// The invert path's tail behind the decode.  With a neighbourhood filter (a convolution or a rank
-// filter) the decode left plain BGR pixels in d_pix_ (the plan is not fused); each frame goes
-// through the raw kernel (vf_conv.hip, vf_rank.hip) into d_pix2_ at the same offset and the encoder
-// reads that.  settle_decode's tails call this, so a batch resynchronised at wait_invert is
-// filtered again from freshly decoded pixels: once.
+// The invert path's tail behind the decode.  With a program (vf_chain_plan.h; a convolution or a
+// rank filter is one of a single step) the decode left plain BGR pixels in d_pix_ (the plan is not
+// fused).  Per frame the program's whole-frame launches run through the one executor
+// (vf_api.hip), value v in buffer bufs.of[v] at the frame's d_pix_ offset, and the encoder
+// reads the buffer that holds the result.  Buffer 0 is d_pix_ itself: the plan reuses it once the
+// decoded frame is dead, and a resynchronised batch decodes into it again before this runs again.
+// Buffer 1 is d_pix2_, the others d_chain_.  A one-step convolution or rank program has of = {0, 1}:
+// one launch per frame from d_pix_ to d_pix2_ at F.out_off, all rows, form 0.  settle_decode's tails
+// call this, so a batch resynchronised at wait_invert is filtered again from freshly decoded
+// pixels: once.
 int Codec::run_filter_encode(bool fastdct, std::string *err) {
   if (!filter_.between()) return run_encode(1, fastdct, d_pix_.as<uint8_t>(), err);
-  if (filter_.kind == Filter::kChain) {
-    // A program (vf_chain_plan.h): per frame its steps in order on whole frames, value v in buffer
-    // bufs.of[v] at the frame's d_pix_ offset; the encoder reads the buffer that holds the result.
-    // Buffer 0 is d_pix_ itself: the plan reuses it once the decoded frame is dead, and a
-    // resynchronised batch decodes into it again before this runs again.
-    const ChainSpec &c = *filter_.chain;
-    while ((int)d_chain_.size() + 2 < c.bufs.count) d_chain_.emplace_back(new DevBuf());
-    std::vector<uint8_t *> base((size_t)c.bufs.count);
-    for (int k = 0; k < c.bufs.count; ++k) {
-      DevBuf &b = k == 0 ? d_pix_ : k == 1 ? d_pix2_ : *d_chain_[(size_t)k - 2];
-      if (k != 0) CK(b.ensure(dpix_bytes_));  // d_pix_ holds the decoded frames: sized by prepare_decode
-      base[(size_t)k] = b.as<uint8_t>();
-    }
-    const LaunchCfg cfg;
-    const int nst = c.prog.size();
-    for (int f = 0; f < dn_; ++f) {
-      const DecFrame &F = dfr_[(size_t)f];
-      const int w = F.g.w, h = F.g.h;
-      const size_t nbytes = (size_t)w * 3 * (size_t)h;
-      for (int i = 1; i <= nst; ++i) {
-        const chain::Step &st = c.prog.steps[(size_t)i - 1];
-        const uint8_t *a = base[(size_t)c.bufs.of[(size_t)st.a]] + F.out_off;
-        uint8_t *dst = base[(size_t)c.bufs.of[(size_t)i]] + F.out_off;
-        if (st.kind == chain::kTable)
-          CK(launch_lut(a, dst, nbytes, st.table.data(), st.channels, 0, cfg, s_));
-        else if (st.kind == chain::kBinary)
-          CK(launch_binary(a, base[(size_t)c.bufs.of[(size_t)st.b]] + F.out_off, dst, nbytes, st.op, cfg, s_));
-        else if (st.kind == chain::kConv)
-          CK(launch_conv(a, dst, w, 3, h, 0, h, 0, h, st.weights.data(), st.kw, st.kh, st.shift, st.border, 0, s_));
-        else
-          CK(launch_rank(a, dst, w, 3, h, 0, h, 0, h, st.op, c.masks[(size_t)i - 1], st.kw, st.kh, st.border, s_));
-      }
-    }
-    return run_encode(1, fastdct, base[(size_t)c.bufs.result], err);
+  const ChainSpec &c = *filter_.chain;
+  while ((int)d_chain_.size() + 2 < c.bufs.count) d_chain_.emplace_back(new DevBuf());
+  std::vector<uint8_t *> base((size_t)c.bufs.count), at((size_t)c.bufs.count);
+  for (int k = 0; k < c.bufs.count; ++k) {
+    DevBuf &b = k == 0 ? d_pix_ : k == 1 ? d_pix2_ : *d_chain_[(size_t)k - 2];
+    if (k != 0) CK(b.ensure(dpix_bytes_));  // d_pix_ holds the decoded frames: sized by prepare_decode
+    base[(size_t)k] = b.as<uint8_t>();
   }
-  CK(d_pix2_.ensure(dpix_bytes_));
-  const ConvSpec &k = filter_.conv;
-  const RankSpec &r = filter_.rank;
+  const LaunchCfg cfg;
+  std::vector<chain::Launch> launches;  // of a whole frame: they depend on its height alone
+  int launches_h = -1;
   for (int f = 0; f < dn_; ++f) {
     const DecFrame &F = dfr_[(size_t)f];
-    const uint8_t *src = d_pix_.as<uint8_t>() + F.out_off;
-    uint8_t *dst = d_pix2_.as<uint8_t>() + F.out_off;
-    if (filter_.kind == Filter::kRank)
-      CK(launch_rank(src, dst, F.g.w, 3, F.g.h, 0, F.g.h, 0, F.g.h, r.op, r.mask, r.kw, r.kh, r.border, s_));
-    else
-      CK(launch_conv(src, dst, F.g.w, 3, F.g.h, 0, F.g.h, 0, F.g.h, k.w, k.kw, k.kh, k.shift, k.border, 0, s_));
+    const int h = F.g.h;
+    if (h != launches_h) launches = chain::band_launches(c.prog, c.bufs, h, 0, h, 0, false);
+    launches_h = h;
+    for (size_t k = 0; k < base.size(); ++k) at[k] = base[k] + F.out_off;
+    CK(run_launches(c.prog, c.masks.data(), launches, at.data(), nullptr, F.g.w, 3, h, 0, cfg, s_));
   }
-  return run_encode(1, fastdct, d_pix2_.as<uint8_t>(), err);
+  return run_encode(1, fastdct, base[(size_t)c.bufs.result], err);
 }
 
 int Codec::run_encode(int bgr, bool fastdct, const uint8_t *pix, std::string *err) {

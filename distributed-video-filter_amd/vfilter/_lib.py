@@ -446,16 +446,22 @@ class Context:
             raise ValueError("weights must be a C-contiguous kh x kw int16 array (see vfilter.as_kernel)")
         return w
 
-    def conv_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
-                         channels: int, weights, shift: int, border: int = 0) -> None:
+    @staticmethod
+    def _frame_arrays(srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int]):
+        """The pointer and size arrays of a ``*_frames_host`` call over shaped frames, and their length."""
         n = len(srcs)
         if not (len(dsts) == n == len(widths) == len(heights)):
             raise ValueError("srcs, dsts, widths and heights must have the same length")
-        w = self._weights(weights)
         sa = (ctypes.c_void_p * n)(*[_addr(s) for s in srcs])
         da = (ctypes.c_void_p * n)(*[_addr(d) for d in dsts])
         wa = (ctypes.c_int * n)(*[int(v) for v in widths])
         ha = (ctypes.c_int * n)(*[int(v) for v in heights])
+        return sa, da, wa, ha, n
+
+    def conv_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                         channels: int, weights, shift: int, border: int = 0) -> None:
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
+        w = self._weights(weights)
         self._check(self._lib.vf_conv_frames_host(self._ctx, sa, da, wa, ha, n, channels, w.ctypes.data, w.shape[1],
                                                   w.shape[0], shift, border))
 
@@ -476,14 +482,8 @@ class Context:
 
     def rank_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
                          channels: int, op: int, element, border: int = 2) -> None:
-        n = len(srcs)
-        if not (len(dsts) == n == len(widths) == len(heights)):
-            raise ValueError("srcs, dsts, widths and heights must have the same length")
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
         e = self._element(element)
-        sa = (ctypes.c_void_p * n)(*[_addr(s) for s in srcs])
-        da = (ctypes.c_void_p * n)(*[_addr(d) for d in dsts])
-        wa = (ctypes.c_int * n)(*[int(v) for v in widths])
-        ha = (ctypes.c_int * n)(*[int(v) for v in heights])
         self._check(self._lib.vf_rank_frames_host(self._ctx, sa, da, wa, ha, n, channels, op, e.ctypes.data, e.shape[1],
                                                   e.shape[0], border))
 
@@ -520,14 +520,8 @@ class Context:
 
     def chain_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
                           channels: int, steps: Sequence) -> None:
-        n = len(srcs)
-        if not (len(dsts) == n == len(widths) == len(heights)):
-            raise ValueError("srcs, dsts, widths and heights must have the same length")
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
         arr, keep = self._steps(steps)
-        sa = (ctypes.c_void_p * n)(*[_addr(s) for s in srcs])
-        da = (ctypes.c_void_p * n)(*[_addr(d) for d in dsts])
-        wa = (ctypes.c_int * n)(*[int(v) for v in widths])
-        ha = (ctypes.c_int * n)(*[int(v) for v in heights])
         self._check(self._lib.vf_chain_frames_host(self._ctx, sa, da, wa, ha, n, channels, arr, len(steps)))
         del keep
 

@@ -256,6 +256,26 @@ def _conv_frame(name: str, a) -> np.ndarray:
     raise ValueError(f"{name}: a frame is H x W or H x W x 3, not shape {a.shape}")
 
 
+def _frames_call(name: str, srcs: List[np.ndarray], outs: Optional[List], call) -> List:
+    """The frame-list work of ``filter2d_frames``, ``rank_frames`` and ``chain_frames`` (``name``, for the
+    messages) on checked frames: one channel count, ``outs`` made or checked, and
+    ``call(srcs, outs, widths, heights, channels)`` on the frames that are not empty."""
+    srcs = [np.ascontiguousarray(s) for s in srcs]
+    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
+    if len(chans) > 1:
+        raise ValueError(f"{name}: the frames of one call have one channel count")
+    if outs is None:
+        outs = [np.empty_like(s) for s in srcs]
+    elif len(outs) != len(srcs) or any(o.shape != s.shape or o.dtype != np.uint8 or not o.flags.c_contiguous
+                                       for o, s in zip(outs, srcs)):
+        raise ValueError(f"{name}: outs must be C-contiguous uint8 arrays of the frames' shapes")
+    live = [(s, o) for s, o in zip(srcs, outs) if s.size]
+    if live:
+        call([s for s, _ in live], [o for _, o in live], [s.shape[1] for s, _ in live],
+             [s.shape[0] for s, _ in live], chans.pop())
+    return outs
+
+
 def filter2d(src: np.ndarray, kernel, dst: Optional[np.ndarray] = None, border: str = "reflect101",
              ctx: Optional[Context] = None) -> np.ndarray:
     """Drop-in for ``cv2.filter2D(src, -1, kernel)`` on uint8 ``H x W`` or ``H x W x 3`` input
@@ -265,10 +285,7 @@ def filter2d(src: np.ndarray, kernel, dst: Optional[np.ndarray] = None, border: 
     weights, shift = as_kernel(kernel)
     code = border_code(border)
     src = np.ascontiguousarray(_conv_frame("filter2d", src))
-    if dst is None:
-        dst = np.empty_like(src)
-    elif not isinstance(dst, np.ndarray) or dst.shape != src.shape or dst.dtype != src.dtype or not dst.flags.c_contiguous:
-        raise ValueError("filter2d: dst must be C-contiguous with src's shape and dtype")
+    dst = _rank_dst("filter2d", src, dst)
     channels = 1 if src.ndim == 2 else src.shape[2]
     if src.size:
         (ctx or get_context()).conv_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, weights, shift,
@@ -282,21 +299,8 @@ def filter2d_frames(frames: Sequence, kernel, outs: Optional[List] = None, borde
     Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
     weights, shift = as_kernel(kernel)
     code = border_code(border)
-    srcs = [np.ascontiguousarray(_conv_frame("filter2d_frames", f)) for f in frames]
-    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
-    if len(chans) > 1:
-        raise ValueError("filter2d_frames: the frames of one call have one channel count")
-    if outs is None:
-        outs = [np.empty_like(s) for s in srcs]
-    elif len(outs) != len(srcs) or any(o.shape != s.shape or o.dtype != np.uint8 or not o.flags.c_contiguous
-                                       for o, s in zip(outs, srcs)):
-        raise ValueError("filter2d_frames: outs must be C-contiguous uint8 arrays of the frames' shapes")
-    live = [(s, o) for s, o in zip(srcs, outs) if s.size]
-    if live:
-        (ctx or get_context()).conv_frames_host([s for s, _ in live], [o for _, o in live],
-                                                [s.shape[1] for s, _ in live], [s.shape[0] for s, _ in live],
-                                                chans.pop(), weights, shift, code)
-    return outs
+    return _frames_call("filter2d_frames", [_conv_frame("filter2d_frames", f) for f in frames], outs,
+                        lambda *a: (ctx or get_context()).conv_frames_host(*a, weights, shift, code))
 
 
 # -- rank filters: cv2.erode, cv2.dilate, cv2.medianBlur ------------------------------------------
@@ -432,21 +436,8 @@ def rank_frames(frames: Sequence, rank: Rank, outs: Optional[List] = None, ctx: 
     call.  Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
     if not isinstance(rank, Rank):
         raise ValueError("rank_frames: rank is a vfilter.Rank (Rank.erode, Rank.dilate, Rank.median)")
-    srcs = [np.ascontiguousarray(_conv_frame("rank_frames", f)) for f in frames]
-    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
-    if len(chans) > 1:
-        raise ValueError("rank_frames: the frames of one call have one channel count")
-    if outs is None:
-        outs = [np.empty_like(s) for s in srcs]
-    elif len(outs) != len(srcs) or any(o.shape != s.shape or o.dtype != np.uint8 or not o.flags.c_contiguous
-                                       for o, s in zip(outs, srcs)):
-        raise ValueError("rank_frames: outs must be C-contiguous uint8 arrays of the frames' shapes")
-    live = [(s, o) for s, o in zip(srcs, outs) if s.size]
-    if live:
-        (ctx or get_context()).rank_frames_host([s for s, _ in live], [o for _, o in live],
-                                                [s.shape[1] for s, _ in live], [s.shape[0] for s, _ in live],
-                                                chans.pop(), *rank.args)
-    return outs
+    return _frames_call("rank_frames", [_conv_frame("rank_frames", f) for f in frames], outs,
+                        lambda *a: (ctx or get_context()).rank_frames_host(*a, *rank.args))
 
 
 # -- filter chains: a program of filters between one upload and one download ----------------------
@@ -654,21 +645,8 @@ def chain_frames(frames: Sequence, chain, outs: Optional[List] = None, ctx: Opti
     """A ``Chain`` over separately stored frames of one channel count and mixed sizes in one call.
     Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
     c = _as_chain(chain)
-    srcs = [np.ascontiguousarray(_chain_frame("chain_frames", f, c)) for f in frames]
-    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
-    if len(chans) > 1:
-        raise ValueError("chain_frames: the frames of one call have one channel count")
-    if outs is None:
-        outs = [np.empty_like(s) for s in srcs]
-    elif len(outs) != len(srcs) or any(o.shape != s.shape or o.dtype != np.uint8 or not o.flags.c_contiguous
-                                       for o, s in zip(outs, srcs)):
-        raise ValueError("chain_frames: outs must be C-contiguous uint8 arrays of the frames' shapes")
-    live = [(s, o) for s, o in zip(srcs, outs) if s.size]
-    if live:
-        (ctx or get_context()).chain_frames_host([s for s, _ in live], [o for _, o in live],
-                                                 [s.shape[1] for s, _ in live], [s.shape[0] for s, _ in live],
-                                                 chans.pop(), *c.args)
-    return outs
+    return _frames_call("chain_frames", [_chain_frame("chain_frames", f, c) for f in frames], outs,
+                        lambda *a: (ctx or get_context()).chain_frames_host(*a, *c.args))
 
 
 def morphology_ex(src: np.ndarray, op: str, element=None, iterations: int = 1, dst: Optional[np.ndarray] = None,

@@ -7,9 +7,10 @@
 //   grid       a scalar model of each step run band by band (vf_conv_bands.h with ry = R), reading
 //              only rows the plan says exist, borders in frame coordinates, equals the whole frame
 //   random     seeded programs over the whole step space (oblong sides, a border per step, a == b,
-//              shared tables): validate accepts, fold keeps the picture, the schedule holds, and an
-//              executor that stores values in the plan's buffers at the band's row origin, in place
-//              where the plan says so, equals the whole frame for every capacity from 2 R + 1 rows up
+//              shared tables): validate accepts, fold keeps the picture, the schedule holds, and the
+//              library's own launch list (band_launches, what run_launches walks) run on byte buffers
+//              equals the whole frame for every capacity from 2 R + 1 rows up, and for the whole frame
+//              with the result left in its buffer; a one-step program is one launch with no scratch
 //   plan       the reach, the folded steps and the buffers of serialised programs, for the tests that
 //              compare them with tests/_chain_ref.py and name features of tests/_chain_gen.py's set
 #include <cstdio>
@@ -299,6 +300,25 @@ void check_schedule(const Program &p, int *max_count, int *in_place) {
   if (b.count > *max_count) *max_count = b.count;
 }
 
+int g_one_step = 0;
+
+// A program of one step is one launch from buffer 0 to the caller's output rows, with no scratch:
+// what keeps vf_conv_frames_host and vf_rank_frames_host free of allocations beyond the staging.
+void check_one_step(const Program &p, int H) {
+  if (p.size() != 1) return;
+  ++g_one_step;
+  const Buffers bufs = assign_buffers(p);
+  CHECK(scratch_buffers(bufs, p, true) == 0);
+  CHECK(scratch_buffers(bufs, p, false) == bufs.count - 1);
+  const std::vector<Launch> ls = band_launches(p, bufs, H, 0, H, 0, true);
+  CHECK(ls.size() == 1);
+  if (ls.size() != 1) return;
+  const Launch &l = ls[0];
+  CHECK(l.step == 1 && l.a_buf == 0 && l.a_row == 0 && l.dst_buf == kOut && l.dst_row == 0);
+  CHECK(l.y0 == 0 && l.nrows == H && l.src0 == 0 && l.nsrc == H);
+  if (p.steps[0].kind == kBinary) CHECK(l.b_buf == 0 && l.b_row == 0);
+}
+
 int run_buffers() {
   const int B = vf::conv::kConstant;
   Program same;
@@ -315,6 +335,15 @@ int run_buffers() {
   }
   CHECK(assign_buffers(blackhat3_it2(B)).count <= 3 && assign_buffers(edges(B)).count <= 3);
   CHECK(assign_buffers(diamond(B)).count == 2 && assign_buffers(fold(pointwise())).count == 1);
+  for (int H : {1, 7, 40}) {  // a single filter is a one-step program: one launch, no scratch
+    Program one;
+    for (const Step &st : {rank(0, kErode, 3, 5, B), rank(0, kMedian, 5, 5, vf::conv::kReplicate), conv(0, 5, B), table1(0, 0), bin(kAdd, 0, 0)}) {
+      one.steps = {st};
+      check_one_step(one, H);
+    }
+    check_one_step(fold(pointwise()), H);
+  }
+  CHECK(g_one_step == 18);
   std::printf("{\"programs\": %d, \"max_count\": %d, \"in_place\": %d, \"failed\": %d}\n", programs, max_count, in_place,
               g_failed);
   return g_failed ? 1 : 0;
@@ -547,58 +576,76 @@ Program random_program(Lcg &g, int channels) {
   return p;
 }
 
-int g_in_place_run = 0;
+int g_in_place_run = 0, g_launches = 0;
 
-// Rows [b.y0, b.y1) of the (folded) program's result, values stored the way vf_chain_frames_host
-// addresses them: one byte buffer per assign_buffers buffer, all of the band's source rows
-// [b.s0, b.s1); value v's row y at (y - b.s0) * row of its buffer; buffer 0 starts as the upload; a
-// table or binary step reads and writes byte by byte, in place where the plan gives it its
-// operand's buffer; a neighbourhood step gets its operand's first present row as its source, that
-// row's number and the count, and resolves a tap in frame coordinates before moving it into that
-// window; the last step writes the output rows.  tag[k][row] is the value a buffer row holds: a
-// read of a row that does not hold the operand, or an address outside a buffer, is a bad read.
+// Rows [b.y0, b.y1) of the (folded) program's result by the library's own addressing: the launches
+// of band_launches(), walked as run_launches (vf_api.hip) walks them.  One byte buffer per
+// buffer the launches may address (1 + scratch_buffers), each of the band's source rows [b.s0, b.s1);
+// buffer 0 starts as the upload.  Every buffer index, row offset, src0 and nsrc comes from the
+// Launch.  A table or binary step reads and writes byte by byte, in place where its Launch names one
+// buffer row for operand and result; a neighbourhood step resolves a tap in frame coordinates and
+// then moves it into the window [src0, src0 + nsrc) that starts at the operand's a_row.  tag[k][row]
+// is the value and the frame row a buffer row holds: a read of a row that does not hold that row of
+// the operand, or an address outside a buffer, is a bad read.  With result_to_out (the raw path's
+// form) the last step writes the output rows; without (the codec's) the result is read back from
+// its planned buffer.
 std::vector<uint8_t> run_band_buffers(const Program &p, const Frame &f, const std::vector<uint8_t> &img,
-                                      const vf::conv::Band &b) {
+                                      const vf::conv::Band &b, bool result_to_out) {
   const int n = p.size();
   const Buffers bufs = assign_buffers(p);
-  const std::vector<Rows> need = rows_needed(p, f.H, b.y0, b.y1);
+  const std::vector<Launch> ls = band_launches(p, bufs, f.H, b.y0, b.y1, b.s0, result_to_out);
   const size_t row = f.row();
-  const int nsrc_rows = b.s1 - b.s0;
-  std::vector<std::vector<uint8_t>> buf((size_t)bufs.count, std::vector<uint8_t>((size_t)nsrc_rows * row, 0x5A));
-  std::vector<std::vector<int>> tag((size_t)bufs.count, std::vector<int>((size_t)nsrc_rows, -1));
-  std::memcpy(buf[0].data(), img.data() + (size_t)b.s0 * row, (size_t)nsrc_rows * row);
-  for (int &t : tag[0]) t = 0;
+  const int buf_rows = b.s1 - b.s0, nbuf = 1 + scratch_buffers(bufs, p, result_to_out);
+  struct Tag {
+    int value = -1, y = -1;
+  };
+  std::vector<std::vector<uint8_t>> buf((size_t)nbuf, std::vector<uint8_t>((size_t)buf_rows * row, 0x5A));
+  std::vector<std::vector<Tag>> tag((size_t)nbuf, std::vector<Tag>((size_t)buf_rows));
+  std::memcpy(buf[0].data(), img.data() + (size_t)b.s0 * row, (size_t)buf_rows * row);
+  for (int r = 0; r < buf_rows; ++r) tag[0][(size_t)r] = Tag{0, b.s0 + r};
   std::vector<uint8_t> out((size_t)(b.y1 - b.y0) * row, 0xA5);
-  // byte `off` of value v's row y, as at(v, y)[off] addresses it
-  auto load = [&](int v, int y, size_t off) -> uint8_t {
-    const int k = bufs.of[v], r = y - b.s0;
-    if (r < 0 || r >= nsrc_rows || tag[(size_t)k][(size_t)r] != v) {
+  CHECK(nbuf <= bufs.count && (result_to_out || nbuf == bufs.count));
+  CHECK((int)ls.size() == n);
+  // rows [r, r + count) of buffer k lie inside the buffers
+  auto inside = [&](int k, int r, int count) { return k >= 0 && k < nbuf && count > 0 && r >= 0 && r + count <= buf_rows; };
+  // byte `off` of row r of buffer k, which must hold row y of value v
+  auto load = [&](int v, int y, int k, int r, size_t off) -> uint8_t {
+    if (!inside(k, r, 1) || tag[(size_t)k][(size_t)r].value != v || tag[(size_t)k][(size_t)r].y != y) {
       ++g_bad_reads;
       return 0x5A;
     }
     return buf[(size_t)k][(size_t)r * row + off];
   };
-  for (int i = 1; i <= n; ++i) {
-    const Step &s = p.steps[i - 1];
-    const Rows r = need[i], ra = need[s.a];
-    const int k = bufs.of[i];
-    CHECK(r.lo >= b.s0 && r.hi <= b.s1 && r.lo < r.hi);
-    if (r.lo < b.s0 || r.hi > b.s1) return out;
-    if (i < n && (k == bufs.of[s.a] || (s.kind == kBinary && k == bufs.of[s.b]))) {
-      CHECK(!is_neighbourhood(s));
+  for (size_t li = 0; li < ls.size(); ++li) {
+    const Launch &l = ls[li];
+    ++g_launches;
+    CHECK(l.step == (int)li + 1);
+    if (l.step < 1 || l.step > n) return out;
+    const Step &s = p.steps[(size_t)l.step - 1];
+    const bool to_out = l.dst_buf == kOut;
+    CHECK(to_out == (result_to_out && l.step == n));
+    // every (buffer, row) the launch names lies inside 1 + scratch_buffers buffers of s1 - s0 rows
+    const bool addressed = inside(l.a_buf, l.a_row, l.nsrc) && (s.kind != kBinary || inside(l.b_buf, l.b_row, l.nrows)) &&
+                           (to_out ? l.dst_row == 0 && l.y0 == b.y0 && l.nrows == b.y1 - b.y0 : inside(l.dst_buf, l.dst_row, l.nrows));
+    CHECK(addressed);
+    if (!addressed) return out;
+    CHECK(is_neighbourhood(s) || l.nsrc == l.nrows);
+    if (!to_out && (l.dst_buf == l.a_buf || (s.kind == kBinary && l.dst_buf == l.b_buf))) {
+      CHECK(!is_neighbourhood(s));  // a neighbourhood step never runs in place
+      CHECK(l.dst_row == (l.dst_buf == l.a_buf ? l.a_row : l.b_row));  // in place is dst == operand exactly
       ++g_in_place_run;
     }
-    for (int y = r.lo; y < r.hi; ++y) {
+    for (int yy = 0; yy < l.nrows; ++yy) {
+      const int y = l.y0 + yy;
       for (size_t off = 0; off < row; ++off) {
         const int x = (int)(off / (size_t)f.C), c = (int)(off % (size_t)f.C);
         int q = 0;
         if (s.kind == kTable) {
-          q = through(s, c, load(s.a, y, off));
+          q = through(s, c, load(s.a, y, l.a_buf, l.a_row + yy, off));
         } else if (s.kind == kBinary) {
-          const int a = load(s.a, y, off), bb = load(s.b, y, off);
+          const int a = load(s.a, y, l.a_buf, l.a_row + yy, off), bb = load(s.b, y, l.b_buf, l.b_row + yy, off);
           q = s.op == kSubtract ? a - bb : s.op == kAdd ? a + bb : s.op == kAbsdiff ? std::abs(a - bb) : s.op == kMin ? (a < bb ? a : bb) : (a > bb ? a : bb);
         } else {
-          const int src_s0 = ra.lo, src_n = ra.hi - ra.lo;  // launch_conv / launch_rank's s0 and nsrc
           int acc = 0, mn = 255, mx = 0, cnt = 0;
           int med[49];
           for (int j = 0; j < s.kh; ++j)
@@ -607,10 +654,10 @@ std::vector<uint8_t> run_band_buffers(const Program &p, const Frame &f, const st
               const int by = vf::conv::border_index(y + j - s.kh / 2, f.H, s.border);
               const int bx = vf::conv::border_index(x + t - s.kw / 2, f.W, s.border);
               if (by < 0 || bx < 0) continue;
-              const int sr = by - src_s0;
+              const int sr = by - l.src0;  // launch_conv / launch_rank's s0 and nsrc
               int v = 0x5A;
-              if (sr < 0 || sr >= src_n) ++g_bad_reads;  // the kernel would stage a neutral value here
-              else v = load(s.a, src_s0 + sr, (size_t)bx * f.C + c);
+              if (sr < 0 || sr >= l.nsrc) ++g_bad_reads;  // the kernel would stage a neutral value here
+              else v = load(s.a, by, l.a_buf, l.a_row + sr, (size_t)bx * f.C + c);
               acc += s.kind == kConv ? v * s.weights[(size_t)j * s.kw + t] : 0;
               mn = v < mn ? v : mn, mx = v > mx ? v : mx;
               med[cnt++] = v;
@@ -625,12 +672,16 @@ std::vector<uint8_t> run_band_buffers(const Program &p, const Frame &f, const st
           }
         }
         const uint8_t byte = (uint8_t)(q < 0 ? 0 : q > 255 ? 255 : q);
-        if (i == n) out[(size_t)(y - r.lo) * row + off] = byte;
-        else buf[(size_t)k][(size_t)(y - b.s0) * row + off] = byte;
+        if (to_out) out[(size_t)(l.dst_row + yy) * row + off] = byte;
+        else buf[(size_t)l.dst_buf][(size_t)(l.dst_row + yy) * row + off] = byte;
       }
-      if (i < n) tag[(size_t)k][(size_t)(y - b.s0)] = i;
+      if (!to_out) tag[(size_t)l.dst_buf][(size_t)(l.dst_row + yy)] = Tag{l.step, y};
     }
   }
+  if (!result_to_out)  // the encoder's read: the result's rows from the buffer the plan reports
+    for (int y = b.y0; y < b.y1; ++y)
+      for (size_t off = 0; off < row; ++off)
+        out[(size_t)(y - b.y0) * row + off] = load(n, y, bufs.result, y - b.s0, off);
   return out;
 }
 
@@ -643,7 +694,7 @@ bool has_table3(const Program &p) {
 int run_random(int count) {
   Lcg g{20240607u};
   int programs = 0, cases = 0, multi_band = 0, bands_run = 0, folded = 0, max_count = 0, in_place = 0, max_reach = 0;
-  int oblong = 0, one_row = 0;
+  int oblong = 0, one_row = 0, codec_form = 0;
   for (int k = 0; k < count; ++k) {
     const int channels = k & 1 ? 3 : 1;
     const Program p = random_program(g, channels);
@@ -673,6 +724,13 @@ int run_random(int count) {
           const Val whole = run_band(p, f, img, 0, H, 0, H);
           const Val whole_folded = run_band(fp, f, img, 0, H, 0, H);
           CHECK(whole.d == whole_folded.d);
+          // the codec's form: the whole frame at once, the result left in its planned buffer
+          const bool codec_same = run_band_buffers(fp, f, img, vf::conv::Band{0, H, 0, H}, false) == whole.d;
+          if (!codec_same && g_failed < 20)
+            std::fprintf(stderr, "program %d, %d x %d x %d: the whole frame with the result in its buffer differs\n", k, W, H, C);
+          CHECK(codec_same);
+          ++codec_form;
+          check_one_step(fp, H);
           const int need_rows = 2 * R + 1 < H ? 2 * R + 1 : H;
           for (int rows = need_rows; rows <= H + 1; ++rows) {
             std::vector<vf::conv::Band> bs;
@@ -685,7 +743,7 @@ int run_random(int count) {
             for (const vf::conv::Band &b : bs) {
               CHECK(b.y0 == next && b.y1 > b.y0 && b.s1 - b.s0 <= rows);
               next = b.y1;
-              const std::vector<uint8_t> got = run_band_buffers(fp, f, img, b);
+              const std::vector<uint8_t> got = run_band_buffers(fp, f, img, b, true);
               ++bands_run;
               const bool same = std::memcmp(got.data(), whole.d.data() + (size_t)b.y0 * f.row(), got.size()) == 0;
               if (!same && g_failed < 20)
@@ -699,10 +757,10 @@ int run_random(int count) {
   }
   CHECK(g_bad_reads == 0);
   std::printf("{\"programs\": %d, \"cases\": %d, \"multi_band\": %d, \"bands\": %d, \"folded\": %d, \"max_count\": %d, "
-              "\"in_place\": %d, \"in_place_run\": %d, \"max_reach\": %d, \"oblong\": %d, \"one_row\": %d, \"bad_reads\": %d, "
-              "\"failed\": %d}\n",
+              "\"in_place\": %d, \"in_place_run\": %d, \"max_reach\": %d, \"oblong\": %d, \"one_row\": %d, \"codec_form\": %d, "
+              "\"one_step\": %d, \"launches\": %d, \"bad_reads\": %d, \"failed\": %d}\n",
               programs, cases, multi_band, bands_run, folded, max_count, in_place, g_in_place_run, max_reach, oblong, one_row,
-              g_bad_reads, g_failed);
+              codec_form, g_one_step, g_launches, g_bad_reads, g_failed);
   return g_failed ? 1 : 0;
 }
 

@@ -11,11 +11,14 @@ equals the whole-frame result, for the programs ``edges``, ``blackhat3_it2`` and
 
 Its ``random`` mode draws 500 seeded programs over the whole step space (``tests/_chain_gen.py``'s:
 oblong kernels and elements, a border per step, ``a == b``, shared tables) and runs the buffer
-schedule and the row plan together: an executor that keeps one byte buffer per planned buffer, puts
-value ``v``'s row ``y`` at ``(y - band.s0) * row`` as ``vf_chain_frames_host`` does, and runs table
-and binary steps in place where the plan says so.  Its ``plan`` mode prints the plan of the programs
-of ``tests/_chain_gen.py``, so that the reach of ``tests/_chain_ref.py`` and the features that need
-the plan (folding, buffers) are checked against the library's own text.
+schedule and the row plan together through the library's own executor addressing: it walks
+``band_launches()``, the list both GPU paths hand to ``run_launches`` (``csrc/vf_api.hip``), on
+byte buffers, and takes every buffer index, row offset, ``src0`` and ``nsrc`` from a ``Launch`` -- band
+by band with the last step writing the output rows (the raw path's form), and once per frame with
+the result left in its planned buffer (the codec's).  Table and binary steps run in place where the
+launch says so; a one-step program is one launch with no scratch.  Its ``plan`` mode prints the plan
+of the programs of ``tests/_chain_gen.py``, so that the reach of ``tests/_chain_ref.py`` and the
+features that need the plan (folding, buffers) are checked against the library's own text.
 """
 import json
 import os
@@ -87,6 +90,8 @@ def test_random_programs_through_the_schedule_and_the_row_plan_together(checker)
     assert out["failed"] == 0 and out["bad_reads"] == 0, out
     assert out["programs"] >= 500 and out["multi_band"] > 0 and out["in_place"] > 0 and out["in_place_run"] > 0, out
     assert out["folded"] > 0 and out["oblong"] > 0 and out["one_row"] > 0 and out["max_reach"] >= 9, out
+    # both calling forms of the launch list ran, and single filters among them
+    assert out["codec_form"] > 0 and out["one_step"] > 0 and out["launches"] > out["bands"], out
 
 
 @pytest.fixture(scope="module")

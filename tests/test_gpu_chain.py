@@ -150,6 +150,27 @@ def test_bands_of_a_frame_larger_than_the_staging():
             assert np.array_equal(o, CR.run(f, ps["diamond"])), f.shape
 
 
+def test_a_one_step_chain_is_the_single_filter_band_by_band():
+    """A convolution or a rank filter runs as a program of one step, so ``chain_frames`` with that one
+    step and the single filter's call give the same bytes: on a 1024 x 800 x 3 frame in 1 MiB of
+    staging (three bands) and on a 7 x 5 x 1 frame, out of place and with ``dst`` the source."""
+    k5 = vfilter.kernels.gaussian5()
+    e35 = R.element_set()["rect3x5"]
+    frames = [CR.noise(800, 1024, 3, seed=5), CR.noise(5, 7, 1, seed=7)]
+    with vfilter.Context(0, max_frame_bytes=1 << 20, max_batch=1) as ctx:
+        singles = [(Kernel(k5), lambda fs, outs=None: vfilter.filter2d_frames(fs, k5, outs, ctx=ctx)),
+                   (Rank.erode(e35), lambda fs, outs=None: vfilter.rank_frames(fs, Rank.erode(e35), outs, ctx=ctx))]
+        for step, single in singles:
+            for f in frames:
+                want = single([f])[0]
+                assert want.shape == f.shape and want.any() and not np.array_equal(want, f)
+                got = vfilter.chain_frames([f], [step], ctx=ctx)[0]
+                assert np.array_equal(got, want), (step.family, f.shape, np.argwhere(got != want)[:5])
+                a, b = f.copy(), f.copy()  # dst is src: a band's halo rows are the band before's output
+                assert vfilter.chain_frames([a], [step], outs=[a], ctx=ctx)[0] is a and single([b], [b])[0] is b
+                assert np.array_equal(a, want) and np.array_equal(b, want), (step.family, f.shape, "in place")
+
+
 def test_rows_that_do_not_fit_the_staging_raise_and_the_context_goes_on():
     # 1 MiB of staging, rows of 131,072 x 3 bytes: two rows fit, blackhat3_it2 needs 2 R + 1 = 9
     wide = CR.noise(12, 131072, 3, seed=6)
