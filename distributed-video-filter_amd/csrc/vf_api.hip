@@ -35,7 +35,7 @@
 #include "vf_jpeg_codec.h"
 #include "vf_lut_split.h"
 #include "vf_conv_bands.h"
-#include "vf_conv_border.h"
+#include "vf_tile_plan.h"
 #include "vf_chain_plan.h"
 
 #define VF_EXPORT extern "C" __attribute__((visibility("default")))
@@ -477,15 +477,14 @@ namespace {
 // The kernel arguments every vf_conv_* / vf_jpeg_conv* entry point shares.
 int check_kernel(vf_ctx *ctx, const char *fn, const int16_t *weights, int kw, int kh, int shift, int border) {
   if (!weights) return set_err(ctx, VF_E_INVALID, 0, "%s: weights is NULL", fn);
-  if (kw < 1 || kh < 1 || kw > vf::conv::kMaxK || kh > vf::conv::kMaxK || !(kw & 1) || !(kh & 1))
+  if (!vf::tile::sides_ok(kw, kh))
     return set_err(ctx, VF_E_INVALID, 0, "%s: a %d x %d kernel; sides are odd and at most %d", fn, kw, kh,
                    vf::conv::kMaxK);
   if (shift < 0 || shift > 16) return set_err(ctx, VF_E_INVALID, 0, "%s: shift=%d outside 0..16", fn, shift);
   long sum = 0;
   for (int i = 0; i < kw * kh; ++i) sum += std::labs((long)weights[i]);
   if (sum > 65536) return set_err(ctx, VF_E_INVALID, 0, "%s: sum|K| = %ld exceeds 65536", fn, sum);
-  if (border != VF_BORDER_REFLECT101 && border != VF_BORDER_REPLICATE && border != VF_BORDER_CONSTANT)
-    return set_err(ctx, VF_E_INVALID, 0, "%s: unknown border %d", fn, border);
+  if (!vf::tile::border_ok(border)) return set_err(ctx, VF_E_INVALID, 0, "%s: unknown border %d", fn, border);
   return VF_OK;
 }
 
@@ -692,11 +691,10 @@ int check_rank(vf_ctx *ctx, const char *fn, int op, const uint8_t *element, int 
   if (op != VF_RANK_ERODE && op != VF_RANK_DILATE && op != VF_RANK_MEDIAN)
     return set_err(ctx, VF_E_INVALID, 0, "%s: unknown op %d", fn, op);
   if (!element) return set_err(ctx, VF_E_INVALID, 0, "%s: element is NULL", fn);
-  if (kw < 1 || kh < 1 || kw > vf::conv::kMaxK || kh > vf::conv::kMaxK || !(kw & 1) || !(kh & 1))
+  if (!vf::tile::sides_ok(kw, kh))
     return set_err(ctx, VF_E_INVALID, 0, "%s: a %d x %d element; sides are odd and at most %d", fn, kw, kh,
                    vf::conv::kMaxK);
-  if (border != VF_BORDER_REFLECT101 && border != VF_BORDER_REPLICATE && border != VF_BORDER_CONSTANT)
-    return set_err(ctx, VF_E_INVALID, 0, "%s: unknown border %d", fn, border);
+  if (!vf::tile::border_ok(border)) return set_err(ctx, VF_E_INVALID, 0, "%s: unknown border %d", fn, border);
   *mask = vf::rank_mask(element, kw, kh);
   if (*mask == 0) return set_err(ctx, VF_E_INVALID, 0, "%s: an empty element (no member)", fn);
   if (op == VF_RANK_MEDIAN) {

@@ -114,20 +114,11 @@ template <int OP>
 hipError_t launch_op(const uint8_t *a, const uint8_t *b, uint8_t *dst, size_t nbytes, int max_blocks,
                      hipStream_t stream) {
   constexpr int U = 4;
-  // head (bytes until dst's 16-B boundary), body (whole vectors), tail
-  const uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
-  const uint32_t h = head < nbytes ? head : (uint32_t)nbytes;
-  const uint64_t rest = nbytes - h;
-  const uint64_t n16 = rest >> 4;
-  const uint32_t tail = (uint32_t)(rest & 15);
-  constexpr uint64_t TILE = (uint64_t)kBlock * U;
-  const uint64_t tiles = (n16 + TILE - 1) / TILE;
-  uint64_t blocks = tiles ? tiles : 1;
-  if (blocks > (uint64_t)max_blocks) blocks = (uint64_t)max_blocks;
-  const uint64_t body = n16 << 4;
-  hipLaunchKernelGGL((binary_kernel<OP, U>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, a + h, b + h,
-                     reinterpret_cast<u32x4 *>(dst + h), n16, a, b, dst, h, a + h + body, b + h + body,
-                     dst + h + body, tail);
+  const stream::Split s = stream::split(dst, nbytes);  // the 16-B grid is dst's
+  const size_t t = s.tail_at();
+  hipLaunchKernelGGL((binary_kernel<OP, U>), dim3(stream::blocks(s.n16, (uint64_t)kBlock * U, max_blocks)), dim3(kBlock),
+                     0, stream, a + s.head, b + s.head, reinterpret_cast<u32x4 *>(dst + s.head), s.n16, a, b, dst, s.head,
+                     a + t, b + t, dst + t, s.tail);
   return hipGetLastError();
 }
 

@@ -6,17 +6,15 @@
 // kernel works on bytes and never de-interleaves.  A workgroup (256 lanes) owns a tile of
 // kTileRows rows x kTileBytes row bytes:
 //   * staging: the tile with its halo, (kTileRows + 2 R) rows x kStageBytes bytes, goes into LDS
-//     in 16-B pieces (aligned 16-B loads where the source allows).  Borders are resolved here, in
-//     frame coordinates (vf_conv_border.h): a piece that leaves the row, or a row outside the
-//     frame, is put together byte by byte, so the inner loop has no border branches;
+//     in 16-B pieces with the borders resolved, in frame coordinates (vf_conv_border.h): a piece
+//     that leaves the row is put together byte by byte, so the inner loop has no border branches;
 //   * compute: lane (lx, ly) produces 16 adjacent bytes of row ly.  Per kernel row it reads one
 //     64-B window of LDS (8-B aligned; the row pitch is 2 banks off a multiple of 64, so the two
 //     rows a 32-lane group touches would not collide as b64 reads -- the compiler drops the dwords
 //     no tap uses and reads the rest as ds_read2_b32 pairs, which do: DESIGN.md 16.3) and every
 //     tap is a compile-time byte of that window;
-//   * store: 16 B per lane, nontemporal, when the address is 16-B aligned (always, for a frame
-//     whose W * C is a multiple of 16 at an aligned pointer); otherwise dwords or bytes, and a
-//     row's last partial piece bytewise.
+//   * store: 16 B per lane, nontemporal, when the address is 16-B aligned (always,
+//     for W * C a multiple of 16 at an aligned pointer); otherwise dwords or bytes.
 // Two arithmetic forms, both exact, chosen on the host from K alone (conv_form):
 //   wide    one 32-bit multiply-add per tap and byte;
 //   narrow  packed 16-bit multiply-adds on byte pairs, when sum|K| * 255 < 2^15.
@@ -39,16 +37,11 @@ namespace vf {
 
 namespace {
 
-using namespace tile;  // the shared tile geometry and load16_any (vf_tile.h)
+using namespace tile;  // the tile geometry, row arguments and window both kernels share (vf_tile.h)
 
 struct ConvArgs {
-  const uint8_t *src;  // frame row s0, byte 0
-  uint8_t *dst;        // frame row y0, byte 0
-  uint32_t row_bytes;  // W * C
-  int32_t w, h;        // the frame
-  int32_t y0, nrows;   // output rows [y0, y0 + nrows)
-  int32_t s0, nsrc;    // source rows present [s0, s0 + nsrc)
-  int32_t border, shift;
+  Rows r;
+  int32_t shift;
   int16_t k[conv::kMaxK * conv::kMaxK];  // KS * KS weights, row-major
 };
 
@@ -58,15 +51,6 @@ __device__ __forceinline__ int win_byte(const uint32_t (&w)[16], int idx) {
 }
 
 typedef short short2v __attribute__((ext_vector_type(2)));
-
-// bytes idx and idx + 1 of the window, zero-extended into the two halves of a dword
-__device__ __forceinline__ short2v win_pair(const uint32_t (&w)[16], int idx) {
-  const int d = idx >> 2, k = idx & 3;
-  uint32_t r;
-  if (k < 3) r = __builtin_amdgcn_perm(0u, w[d], 0x0C000C00u | (uint32_t)(k + 1) << 16 | (uint32_t)k);
-  else r = __builtin_amdgcn_perm(w[d + 1], w[d], 0x0C040C03u);
-  return __builtin_bit_cast(short2v, r);
-}
 
 __device__ __forceinline__ uint32_t finish(int acc, int shift, int bias, int odd) {
   // round half to even: floor((acc + h - 1 + (floor(acc / 2^shift) is odd)) / 2^shift); shift 0: acc
@@ -81,8 +65,8 @@ __global__ __launch_bounds__(kBlock) void conv_kernel(const ConvArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[SR * kPitch];
   const int tid = (int)threadIdx.x;
   const int64_t tile_x = (int64_t)blockIdx.x * kTileBytes;  // row offset of the tile's first byte
-  const int ty0 = a.y0 + (int)blockIdx.y * kTileRows;       // frame row of the tile's first row
-  const int yend = a.y0 + a.nrows;
+  const int ty0 = a.r.y0 + (int)blockIdx.y * kTileRows;     // frame row of the tile's first row
+  const int yend = a.r.y0 + a.r.nrows;
 
   // ---- stage the tile and its halo, borders resolved ------------------------------------------
   for (int item = tid; item < SR * kPieces; item += kBlock) {
@@ -91,12 +75,12 @@ __global__ __launch_bounds__(kBlock) void conv_kernel(const ConvArgs a) {
     u32x4 v;
     v.x = v.y = v.z = v.w = 0;
     if (fy_raw < yend + R) {  // rows below the last output row's halo are never read
-      const int fy = conv::border_index(fy_raw, a.h, a.border);
-      const int sr = fy - a.s0;
-      if (fy >= 0 && sr >= 0 && sr < a.nsrc) {
-        const uint8_t *row = a.src + (size_t)sr * a.row_bytes;
+      const int fy = conv::border_index(fy_raw, a.r.h, a.r.border);
+      const int sr = fy - a.r.s0;
+      if (fy >= 0 && sr >= 0 && sr < a.r.nsrc) {
+        const uint8_t *row = a.r.src + (size_t)sr * a.r.row_bytes;
         const int64_t o = tile_x - kHalo + 16 * c;  // row offset of the piece
-        if (o >= 0 && o + 16 <= (int64_t)a.row_bytes) {
+        if (o >= 0 && o + 16 <= (int64_t)a.r.row_bytes) {
           v = load16_any(row + o);
         } else {
           uint32_t d[4] = {0, 0, 0, 0};
@@ -106,9 +90,9 @@ __global__ __launch_bounds__(kBlock) void conv_kernel(const ConvArgs a) {
             // floor(off / C) for off >= -kHalo
             const int64_t px = (off + (int64_t)kHalo * C) / C - kHalo;
             uint32_t val = 0;
-            if (px >= -R && px < (int64_t)a.w + R) {  // only pixels a tap of the frame can reach
+            if (px >= -R && px < (int64_t)a.r.w + R) {  // only pixels a tap of the frame can reach
               const int ch = (int)(off - px * C);
-              const int bx = conv::border_index((int)px, a.w, a.border);
+              const int bx = conv::border_index((int)px, a.r.w, a.r.border);
               if (bx >= 0) val = row[(size_t)bx * C + ch];
             }
             d[k >> 2] |= val << (8 * (k & 3));
@@ -130,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void conv_kernel(const ConvArgs a) {
   const int lx = tid & 15, ly = tid >> 4;
   const int y = ty0 + ly;
   const int64_t o = tile_x + 16 * lx;
-  if (y >= yend || o >= (int64_t)a.row_bytes) return;
+  if (y >= yend || o >= (int64_t)a.r.row_bytes) return;
   const int shift = a.shift;
   const int bias = shift ? (1 << (shift - 1)) - 1 : 0, odd = shift ? 1 : 0;
   uint32_t q[16];
@@ -140,20 +124,14 @@ __global__ __launch_bounds__(kBlock) void conv_kernel(const ConvArgs a) {
     for (int p = 0; p < 8; ++p) acc[p] = (short2v)(0);
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
-      const uint2 *rp = reinterpret_cast<const uint2 *>(lds + (ly + j) * kPitch + 16 * lx + kWin0);
       uint32_t w[16];
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const uint2 t = rp[m];
-        w[2 * m] = t.x;
-        w[2 * m + 1] = t.y;
-      }
+      load_window(lds, ly + j, lx, w);
 #pragma unroll
       for (int i = 0; i < KS; ++i) {
         const short kk = a.k[j * KS + i];
         const short2v k2 = (short2v)(kk);
 #pragma unroll
-        for (int p = 0; p < 8; ++p) acc[p] += win_pair(w, kWinTile + 2 * p + (i - R) * C) * k2;
+        for (int p = 0; p < 8; ++p) acc[p] += win_pair<short2v>(w, kWinTile + 2 * p + (i - R) * C) * k2;
       }
     }
 #pragma unroll
@@ -167,14 +145,8 @@ __global__ __launch_bounds__(kBlock) void conv_kernel(const ConvArgs a) {
     for (int b = 0; b < 16; ++b) acc[b] = 0;
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
-      const uint2 *rp = reinterpret_cast<const uint2 *>(lds + (ly + j) * kPitch + 16 * lx + kWin0);
       uint32_t w[16];
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const uint2 t = rp[m];
-        w[2 * m] = t.x;
-        w[2 * m + 1] = t.y;
-      }
+      load_window(lds, ly + j, lx, w);
 #pragma unroll
       for (int i = 0; i < KS; ++i) {
         const int kk = a.k[j * KS + i];
@@ -190,8 +162,8 @@ __global__ __launch_bounds__(kBlock) void conv_kernel(const ConvArgs a) {
   for (int m = 0; m < 4; ++m) d[m] = q[4 * m] | q[4 * m + 1] << 8 | q[4 * m + 2] << 16 | q[4 * m + 3] << 24;
 
   // ---- store: inside the row and inside the launch's rows only ------------------------------------
-  uint8_t *dp = a.dst + (size_t)(y - a.y0) * a.row_bytes + o;
-  const int64_t left = (int64_t)a.row_bytes - o;
+  uint8_t *dp = a.r.dst + (size_t)(y - a.r.y0) * a.r.row_bytes + o;
+  const int64_t left = (int64_t)a.r.row_bytes - o;
   if (left >= 16 && ((uintptr_t)dp & 15) == 0) {
     u32x4 v;
     v.x = d[0];
@@ -244,42 +216,22 @@ hipError_t launch_conv(const void *dsrc, void *ddst, int width, int channels, in
                        int nsrc, const int16_t *weights, int kw, int kh, int shift, int border, int form,
                        hipStream_t stream) {
   if (nrows <= 0 || width <= 0) return hipSuccess;
-  if (!dsrc || !ddst || !weights || (channels != 1 && channels != 3) || kw < 1 || kh < 1 || kw > conv::kMaxK ||
-      kh > conv::kMaxK || !(kw & 1) || !(kh & 1) || shift < 0 || shift > 16 || border < 0 || border > 2 ||
-      frame_h <= 0 || y0 < 0 || y0 + (int64_t)nrows > frame_h || s0 < 0 || nsrc <= 0 || s0 + (int64_t)nsrc > frame_h ||
-      (uint64_t)width * (uint64_t)channels > 0x7FFFFFFFull)
+  if (!weights || !rows_ok(dsrc, ddst, width, channels, frame_h, y0, nrows, s0, nsrc) || !sides_ok(kw, kh) ||
+      !border_ok(border) || shift < 0 || shift > 16)
     return hipErrorInvalidValue;
-  const int big = kw > kh ? kw : kh;
-  const int ks = big <= 3 ? 3 : big <= 5 ? 5 : 7;
+  const int ks = square_side(kw, kh);
   ConvArgs a;
   std::memset(&a, 0, sizeof a);
-  // the kw x kh kernel centred in the ks x ks square: the added taps weigh 0, whatever they read
-  const int ox = (ks - kw) / 2, oy = (ks - kh) / 2;
+  // the added taps of the square weigh 0, whatever they read
   for (int j = 0; j < kh; ++j)
-    for (int i = 0; i < kw; ++i) a.k[(j + oy) * ks + i + ox] = weights[j * kw + i];
+    for (int i = 0; i < kw; ++i) a.k[square_at(ks, kw, kh, j, i)] = weights[j * kw + i];
+  a.shift = shift;
   // the narrow form when it holds the kernel; VF_CONV_FORM=wide forces the other, =narrow changes
   // nothing a kernel the narrow form cannot hold
   const bool narrow = form != 1 && conv_narrow_fits(weights, kw * kh);
-  a.row_bytes = (uint32_t)width * (uint32_t)channels;
-  a.w = width;
-  a.h = frame_h;
-  a.s0 = s0;
-  a.nsrc = nsrc;
-  a.border = border;
-  a.shift = shift;
-  a.src = static_cast<const uint8_t *>(dsrc);
-  const unsigned gx = (a.row_bytes + kTileBytes - 1) / kTileBytes;
-  constexpr int kMaxRows = 65535 * kTileRows;  // the grid's y limit
-  for (int done = 0; done < nrows; done += kMaxRows) {
-    const int m = nrows - done < kMaxRows ? nrows - done : kMaxRows;
-    a.y0 = y0 + done;
-    a.nrows = m;
-    a.dst = static_cast<uint8_t *>(ddst) + (size_t)done * a.row_bytes;
-    const dim3 grid(gx, (unsigned)((m + kTileRows - 1) / kTileRows));
-    const hipError_t e = channels == 3 ? launch_c<3>(ks, a, narrow, grid, stream) : launch_c<1>(ks, a, narrow, grid, stream);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return launch_rows(&a.r, dsrc, ddst, width, channels, frame_h, y0, nrows, s0, nsrc, border, [&](dim3 grid) {
+    return channels == 3 ? launch_c<3>(ks, a, narrow, grid, stream) : launch_c<1>(ks, a, narrow, grid, stream);
+  });
 }
 
 }  // namespace vf

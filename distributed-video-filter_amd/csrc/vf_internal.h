@@ -44,8 +44,6 @@ hipError_t launch_lut(const void *dsrc, void *ddst, size_t nbytes, const uint8_t
 // frame_h.  weights: kw * kh int16 in HOST memory, row-major, passed on by value.  border: a
 // conv::k* of vf_conv_border.h.  form: 0 the narrow arithmetic form when it holds the kernel, 1
 // always the wide one, 2 as 0 (conv_form_env reads VF_CONV_FORM = wide | narrow).
-constexpr int kConvTileBytes = 256;  // a workgroup's output tile: row bytes ...
-constexpr int kConvTileRows = 16;    // ... x rows
 hipError_t launch_conv(const void *dsrc, void *ddst, int width, int channels, int frame_h, int y0, int nrows, int s0,
                        int nsrc, const int16_t *weights, int kw, int kh, int shift, int border, int form,
                        hipStream_t stream);

@@ -299,25 +299,19 @@ hipError_t launch_invert_gated(const uint8_t *src, uint8_t *dst, size_t n, const
 
 // src and dst at different offsets mod 16: dst's head bytewise, then the shifting body.
 static hipError_t launch_shift(const uint8_t *s, uint8_t *d, size_t nbytes, int max_blocks, hipStream_t stream) {
-  const uint32_t h = (uint32_t)std::min<size_t>((16 - ((uintptr_t)d & 15)) & 15, nbytes);
-  const uint64_t n16 = (nbytes - h) >> 4;
-  const uint32_t tail = (uint32_t)((nbytes - h) & 15);
+  const stream::Split sp = stream::split(d, nbytes);
+  const uint32_t h = sp.head, tail = sp.tail;
+  const uint64_t n16 = sp.n16;
   const uintptr_t sb = (uintptr_t)(s + h);
   const uint32_t delta = (uint32_t)(sb & 15);  // != 0: the offsets differ mod 16
   const u32x4 *sa = reinterpret_cast<const u32x4 *>(sb - delta);
   u32x4 *d4 = reinterpret_cast<u32x4 *>(d + h);
-  constexpr uint64_t TILE = (uint64_t)kBlock * 4;
-  uint64_t blocks = n16 ? (n16 + TILE - 1) / TILE : 1;
-  if (blocks > (uint64_t)max_blocks) blocks = (uint64_t)max_blocks;
-  const uint8_t *ts = s + h + (n16 << 4);
-  uint8_t *td = d + h + (n16 << 4);
-  const dim3 g((unsigned)blocks), b(kBlock);
-  switch (delta >> 2) {
-    case 0: hipLaunchKernelGGL(invert_shift_kernel<0>, g, b, 0, stream, sa, d4, n16, delta & 3, s, d, h, ts, td, tail); break;
-    case 1: hipLaunchKernelGGL(invert_shift_kernel<1>, g, b, 0, stream, sa, d4, n16, delta & 3, s, d, h, ts, td, tail); break;
-    case 2: hipLaunchKernelGGL(invert_shift_kernel<2>, g, b, 0, stream, sa, d4, n16, delta & 3, s, d, h, ts, td, tail); break;
-    default: hipLaunchKernelGGL(invert_shift_kernel<3>, g, b, 0, stream, sa, d4, n16, delta & 3, s, d, h, ts, td, tail); break;
-  }
+  const uint8_t *ts = s + sp.tail_at();
+  uint8_t *td = d + sp.tail_at();
+  const dim3 g(stream::blocks(n16, (uint64_t)kBlock * 4, max_blocks)), b(kBlock);
+  static constexpr decltype(&invert_shift_kernel<0>) kKernel[4] = {invert_shift_kernel<0>, invert_shift_kernel<1>,
+                                                                   invert_shift_kernel<2>, invert_shift_kernel<3>};
+  hipLaunchKernelGGL(kKernel[delta >> 2], g, b, 0, stream, sa, d4, n16, delta & 3, s, d, h, ts, td, tail);
   return hipGetLastError();
 }
 
@@ -351,8 +345,7 @@ hipError_t launch_invert_mapped(const MappedBatch &b, int n, size_t total_bytes,
   MappedBatch a = b;
   uint64_t tiles = 0;
   for (int k = 0; k < n; ++k) {
-    const uint64_t h = std::min<uint64_t>((16 - ((uintptr_t)a.dst[k] & 15)) & 15, a.n[k]);
-    const uint64_t n16 = (a.n[k] - h) >> 4;
+    const uint64_t n16 = stream::split(a.dst[k], a.n[k]).n16;
     a.tile0[k] = (uint32_t)tiles;
     tiles += n16 ? (n16 + kBlock - 1) / kBlock : 1;  // at least one tile: head and tail bytes
     if (tiles > 0xFFFFFFFFull) return hipErrorInvalidValue;  // > 16 TB in one launch

@@ -171,33 +171,17 @@ template <bool C3, int LAYOUT>
 hipError_t launch_lut_stream(const uint8_t *src, uint8_t *dst, size_t nbytes, uint32_t phase, const LutArg &tab,
                              int max_blocks, hipStream_t stream) {
   constexpr int U = 4;
-  // head (bytes until 16-B alignment), body (whole vectors), tail: launch_stream's split, with
-  // the channel of each part's first byte beside it
-  const uint32_t head = (uint32_t)((16 - ((uintptr_t)src & 15)) & 15);
-  const uint32_t h = head < nbytes ? head : (uint32_t)nbytes;
-  const uint64_t rest = nbytes - h;
-  const uint64_t n16 = rest >> 4;
-  const uint32_t tail = (uint32_t)(rest & 15);
   constexpr uint64_t TILE = (uint64_t)kBlock * U;
-  const uint64_t nchunks = (n16 << 4) > kSplitBytes ? ((n16 << 4) + kChunkBytes - 1) / kChunkBytes : 1;
-  const uint64_t per = nchunks > 1 ? ((n16 + nchunks - 1) / nchunks + TILE - 1) / TILE * TILE : n16;
-  const uint8_t *bs = src + h;
-  uint8_t *bd = dst + h;
-  const uint32_t tail_ph = (uint32_t)((phase + h + n16) % 3);  // 16 = 1 (mod 3)
-  for (uint64_t c0 = 0, k = 0; k == 0 || c0 < n16; c0 += per, ++k) {
-    const uint64_t m = (n16 - c0) < per ? (n16 - c0) : per;
-    const bool first = k == 0, last = c0 + m >= n16;
-    const uint64_t tiles = (m + TILE - 1) / TILE;
-    uint64_t blocks = tiles ? tiles : 1;
-    if (blocks > (uint64_t)max_blocks) blocks = (uint64_t)max_blocks;
-    const uint32_t body_ph = (uint32_t)((phase + h + c0) % 3);
-    const uint32_t phases = body_ph | phase << 2 | tail_ph << 4;
-    hipLaunchKernelGGL((lut_stream_kernel<U, C3, LAYOUT>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                       reinterpret_cast<const u32x4 *>(bs) + c0, reinterpret_cast<u32x4 *>(bd) + c0, m, src, dst,
-                       first ? h : 0u, bs + (n16 << 4), bd + (n16 << 4), last ? tail : 0u, phases, tab);
+  // launch_stream's split and sub-launches, with the channel of each part's first byte beside it
+  const stream::Split s = stream::split(src, nbytes);
+  const u32x4 *bs = reinterpret_cast<const u32x4 *>(src + s.head);
+  u32x4 *bd = reinterpret_cast<u32x4 *>(dst + s.head);
+  for (const stream::Chunk &c : stream::chunks(s.n16, TILE)) {
+    hipLaunchKernelGGL((lut_stream_kernel<U, C3, LAYOUT>), dim3(stream::blocks(c.m, TILE, max_blocks)), dim3(kBlock), 0,
+                       stream, bs + c.c0, bd + c.c0, c.m, src, dst, c.first ? s.head : 0u, src + s.tail_at(),
+                       dst + s.tail_at(), c.last ? s.tail : 0u, stream::phases3(phase, s, c), tab);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (last) break;
   }
   return hipSuccess;
 }

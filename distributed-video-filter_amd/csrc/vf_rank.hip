@@ -2,8 +2,8 @@
 // odd sides up to 7) and cv2.medianBlur (ksize 3 or 5) for uint8 frames of 1 or 3 interleaved
 // channels, exact (DESIGN.md 18 has the definition).  No multiply-adds: min / max on packed bytes.
 //
-// The geometry is vf_conv.hip's.  A workgroup (256 lanes) owns a tile of kConvTileRows rows x
-// kConvTileBytes row bytes:
+// The geometry is vf_conv.hip's.  A workgroup (256 lanes) owns a tile of kTileRows rows x
+// kTileBytes row bytes:
 //   * staging: the tile with its halo goes into LDS in 16-B pieces, borders resolved in frame
 //     coordinates (vf_conv_border.h).  A tap that contributes nothing -- outside the frame under
 //     the constant border, which for erode / dilate means "left out of the set" -- is staged as the
@@ -36,17 +36,11 @@ namespace vf {
 
 namespace {
 
-using namespace tile;  // the shared tile geometry and load16_any (vf_tile.h)
+using namespace tile;  // the tile geometry, row arguments and window both kernels share (vf_tile.h)
 
 struct RankArgs {
-  const uint8_t *src;  // frame row s0, byte 0
-  uint8_t *dst;        // frame row y0, byte 0
-  uint32_t row_bytes;  // W * C
-  int32_t w, h;        // the frame
-  int32_t y0, nrows;   // output rows [y0, y0 + nrows)
-  int32_t s0, nsrc;    // source rows present [s0, s0 + nsrc)
-  int32_t border;
-  uint64_t mask;       // erode / dilate: bit j * KS + i is member (j, i) of the KS x KS square
+  Rows r;
+  uint64_t mask;  // erode / dilate: bit j * KS + i is member (j, i) of the KS x KS square
 };
 
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
@@ -56,30 +50,6 @@ struct PkOps {  // v_pk_min_u16 / v_pk_max_u16, two per us4
   static __device__ __forceinline__ us4 lo(us4 a, us4 b) { return __builtin_elementwise_min(a, b); }
   static __device__ __forceinline__ us4 hi(us4 a, us4 b) { return __builtin_elementwise_max(a, b); }
 };
-
-// bytes idx and idx + 1 of the window, zero-extended into the two halves of a dword
-__device__ __forceinline__ us2 win_pair(const uint32_t (&w)[16], int idx) {
-  const int d = idx >> 2, k = idx & 3;
-  uint32_t r;
-  if (k < 3) r = __builtin_amdgcn_perm(0u, w[d], 0x0C000C00u | (uint32_t)(k + 1) << 16 | (uint32_t)k);
-  else r = __builtin_amdgcn_perm(w[d + 1], w[d], 0x0C040C03u);
-  return __builtin_bit_cast(us2, r);
-}
-
-// the low bytes of two pairs as the four bytes of a dword
-__device__ __forceinline__ uint32_t pack4(us2 a, us2 b) {
-  return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, a), 0x06040200u);
-}
-
-__device__ __forceinline__ void load_window(const uint8_t *lds, int row, int lx, uint32_t (&w)[16]) {
-  const uint2 *rp = reinterpret_cast<const uint2 *>(lds + row * kPitch + 16 * lx + kWin0);
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    const uint2 t = rp[m];
-    w[2 * m] = t.x;
-    w[2 * m + 1] = t.y;
-  }
-}
 
 enum : int { kErode = 0, kDilate = 1, kMedian = 2 };  // VF_RANK_* (include/vfilter.h)
 
@@ -92,8 +62,8 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const RankArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[SR * kPitch];
   const int tid = (int)threadIdx.x;
   const int64_t tile_x = (int64_t)blockIdx.x * kTileBytes;  // row offset of the tile's first byte
-  const int ty0 = a.y0 + (int)blockIdx.y * kTileRows;       // frame row of the tile's first row
-  const int yend = a.y0 + a.nrows;
+  const int ty0 = a.r.y0 + (int)blockIdx.y * kTileRows;     // frame row of the tile's first row
+  const int yend = a.r.y0 + a.r.nrows;
 
   // ---- stage the tile and its halo, borders resolved ------------------------------------------
   for (int item = tid; item < SR * kPieces; item += kBlock) {
@@ -102,12 +72,12 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const RankArgs a) {
     u32x4 v;
     v.x = v.y = v.z = v.w = kNeutral4;
     if (fy_raw < yend + R) {  // rows below the last output row's halo are never read
-      const int fy = conv::border_index(fy_raw, a.h, a.border);
-      const int sr = fy - a.s0;
-      if (fy >= 0 && sr >= 0 && sr < a.nsrc) {
-        const uint8_t *row = a.src + (size_t)sr * a.row_bytes;
+      const int fy = conv::border_index(fy_raw, a.r.h, a.r.border);
+      const int sr = fy - a.r.s0;
+      if (fy >= 0 && sr >= 0 && sr < a.r.nsrc) {
+        const uint8_t *row = a.r.src + (size_t)sr * a.r.row_bytes;
         const int64_t o = tile_x - kHalo + 16 * c;  // row offset of the piece
-        if (o >= 0 && o + 16 <= (int64_t)a.row_bytes) {
+        if (o >= 0 && o + 16 <= (int64_t)a.r.row_bytes) {
           v = load16_any(row + o);
         } else {
           uint32_t d[4] = {0, 0, 0, 0};
@@ -117,9 +87,9 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const RankArgs a) {
             // floor(off / C) for off >= -kHalo
             const int64_t px = (off + (int64_t)kHalo * C) / C - kHalo;
             uint32_t val = kNeutral;
-            if (px >= -R && px < (int64_t)a.w + R) {  // only pixels a tap of the frame can reach
+            if (px >= -R && px < (int64_t)a.r.w + R) {  // only pixels a tap of the frame can reach
               const int ch = (int)(off - px * C);
-              const int bx = conv::border_index((int)px, a.w, a.border);
+              const int bx = conv::border_index((int)px, a.r.w, a.r.border);
               if (bx >= 0) val = row[(size_t)bx * C + ch];
             }
             d[k >> 2] |= val << (8 * (k & 3));
@@ -141,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const RankArgs a) {
   const int lx = tid & 15, ly = tid >> 4;
   const int y = ty0 + ly;
   const int64_t o = tile_x + 16 * lx;
-  if (y >= yend || o >= (int64_t)a.row_bytes) return;
+  if (y >= yend || o >= (int64_t)a.r.row_bytes) return;
   uint32_t d[4];
   if constexpr (OP == kMedian) {
     // 4 output bytes at a time: value (j, i) of the group is the 4 window bytes (i - R) * C away
@@ -155,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const RankArgs a) {
 #pragma unroll
         for (int i = 0; i < KS; ++i) {
           const int at = kWinTile + 4 * g + (i - R) * C;
-          const us2 p0 = win_pair(w, at), p1 = win_pair(w, at + 2);
+          const us2 p0 = win_pair<us2>(w, at), p1 = win_pair<us2>(w, at + 2);
           v[j * KS + i] = us4{p0.x, p0.y, p1.x, p1.y};
         }
       }
@@ -180,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const RankArgs a) {
         if (!((mask >> (j * KS + i)) & 1)) continue;  // wave-uniform: the mask is a kernel argument
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
-          const us2 t = win_pair(w, kWinTile + 2 * p + (i - R) * C);
+          const us2 t = win_pair<us2>(w, kWinTile + 2 * p + (i - R) * C);
           if constexpr (OP == kErode) acc[p] = __builtin_elementwise_min(acc[p], t);
           else acc[p] = __builtin_elementwise_max(acc[p], t);
         }
@@ -191,8 +161,8 @@ __global__ __launch_bounds__(kBlock) void rank_kernel(const RankArgs a) {
   }
 
   // ---- store: inside the row and inside the launch's rows only ------------------------------------
-  uint8_t *dp = a.dst + (size_t)(y - a.y0) * a.row_bytes + o;
-  const int64_t left = (int64_t)a.row_bytes - o;
+  uint8_t *dp = a.r.dst + (size_t)(y - a.r.y0) * a.r.row_bytes + o;
+  const int64_t left = (int64_t)a.r.row_bytes - o;
   if (left >= 16 && ((uintptr_t)dp & 15) == 0) {
     u32x4 v;
     v.x = d[0];
@@ -241,41 +211,21 @@ hipError_t launch_rank(const void *dsrc, void *ddst, int width, int channels, in
                        int nsrc, int op, uint64_t mask, int kw, int kh, int border, hipStream_t stream) {
   if (nrows <= 0 || width <= 0) return hipSuccess;
   const uint64_t full = kw >= 1 && kh >= 1 && kw * kh < 64 ? ((uint64_t)1 << (kw * kh)) - 1 : 0;
-  if (!dsrc || !ddst || (channels != 1 && channels != 3) || kw < 1 || kh < 1 || kw > conv::kMaxK || kh > conv::kMaxK ||
-      !(kw & 1) || !(kh & 1) || op < kErode || op > kMedian || (mask & full) == 0 || (mask & ~full) != 0 || border < 0 ||
-      border > 2 || frame_h <= 0 || y0 < 0 || y0 + (int64_t)nrows > frame_h || s0 < 0 || nsrc <= 0 ||
-      s0 + (int64_t)nsrc > frame_h || (uint64_t)width * (uint64_t)channels > 0x7FFFFFFFull)
+  if (!rows_ok(dsrc, ddst, width, channels, frame_h, y0, nrows, s0, nsrc) || !sides_ok(kw, kh) || !border_ok(border) ||
+      op < kErode || op > kMedian || (mask & full) == 0 || (mask & ~full) != 0)
     return hipErrorInvalidValue;
   if (op == kMedian && (kw != kh || (kw != 3 && kw != 5) || mask != full || border != conv::kReplicate))
     return hipErrorInvalidValue;
-  const int big = kw > kh ? kw : kh;
-  const int ks = big <= 3 ? 3 : big <= 5 ? 5 : 7;
+  const int ks = square_side(kw, kh);
   RankArgs a;
   std::memset(&a, 0, sizeof a);
-  // the kw x kh element centred in the ks x ks square: the added positions are not members
-  const int ox = (ks - kw) / 2, oy = (ks - kh) / 2;
+  // the added positions of the square are not members
   for (int j = 0; j < kh; ++j)
     for (int i = 0; i < kw; ++i)
-      if ((mask >> (j * kw + i)) & 1) a.mask |= (uint64_t)1 << ((j + oy) * ks + i + ox);
-  a.row_bytes = (uint32_t)width * (uint32_t)channels;
-  a.w = width;
-  a.h = frame_h;
-  a.s0 = s0;
-  a.nsrc = nsrc;
-  a.border = border;
-  a.src = static_cast<const uint8_t *>(dsrc);
-  const unsigned gx = (a.row_bytes + kTileBytes - 1) / kTileBytes;
-  constexpr int kMaxRows = 65535 * kTileRows;  // the grid's y limit
-  for (int done = 0; done < nrows; done += kMaxRows) {
-    const int m = nrows - done < kMaxRows ? nrows - done : kMaxRows;
-    a.y0 = y0 + done;
-    a.nrows = m;
-    a.dst = static_cast<uint8_t *>(ddst) + (size_t)done * a.row_bytes;
-    const dim3 grid(gx, (unsigned)((m + kTileRows - 1) / kTileRows));
-    const hipError_t e = channels == 3 ? launch_c<3>(op, ks, a, grid, stream) : launch_c<1>(op, ks, a, grid, stream);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+      if ((mask >> (j * kw + i)) & 1) a.mask |= (uint64_t)1 << square_at(ks, kw, kh, j, i);
+  return launch_rows(&a.r, dsrc, ddst, width, channels, frame_h, y0, nrows, s0, nsrc, border, [&](dim3 grid) {
+    return channels == 3 ? launch_c<3>(op, ks, a, grid, stream) : launch_c<1>(op, ks, a, grid, stream);
+  });
 }
 
 }  // namespace vf

@@ -2,8 +2,8 @@
 ``vfilter.filter2d``) against the numpy reference of ``tests/_conv_ref.py``.  Every comparison
 is exact.
 
-The kernel's output tile is ``kConvTileBytes`` = 256 row bytes x ``kConvTileRows`` = 16 rows
-(csrc/vf_internal.h); a row is W * C bytes and tiles are cut in bytes, so for C = 3 a tile is 85
+The kernel's output tile is ``kTileBytes`` = 256 row bytes x ``kTileRows`` = 16 rows
+(csrc/vf_tile_plan.h); a row is W * C bytes and tiles are cut in bytes, so for C = 3 a tile is 85
 pixels and one byte of the 86th: TW = 85, TH = 16.  The kernel does not grid-stride (one
 workgroup per tile).  The three channels of every image carry different content, and the kernel
 set has an asymmetric 3 wide x 5 high member, so a swapped channel, a flipped or a transposed

@@ -2,8 +2,8 @@
 ``dilate``, ``median_blur``, ``rank_frames``) against the numpy reference of ``tests/_rank_ref.py``.
 Every comparison is exact.
 
-The kernel keeps the convolution's geometry: its output tile is ``kConvTileBytes`` = 256 row bytes
-x ``kConvTileRows`` = 16 rows (csrc/vf_internal.h); a row is W * C bytes and tiles are cut in
+The kernel keeps the convolution's geometry: its output tile is ``kTileBytes`` = 256 row bytes
+x ``kTileRows`` = 16 rows (csrc/vf_tile_plan.h); a row is W * C bytes and tiles are cut in
 bytes, so for C = 3 a tile is 85 pixels and one byte of the 86th: TW = 85, TH = 16.  One
 workgroup per tile, no grid stride.  The channels of every image carry different content; a
 second image holds only the values {0, 1, 2, 3, 252, 253, 254, 255}, so equal values and both
