@@ -556,9 +556,13 @@ hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const
     else if (s.kind == chain::kConv)
       e = launch_conv(a, dst, w, channels, frame_h, l.y0, l.nrows, l.src0, l.nsrc, s.weights.data(), s.kw, s.kh,
                       s.shift, s.border, conv_form, stream);
-    else
+    else if (s.kind == chain::kRank)
       e = launch_rank(a, dst, w, channels, frame_h, l.y0, l.nrows, l.src0, l.nsrc, s.op, masks[l.step - 1], s.kw, s.kh,
                       s.border, stream);
+    else if (s.kind == chain::kMix)
+      e = launch_mix(a, dst, nbytes, s.matrix.data(), s.shift, s.op, cfg, stream);
+    else
+      e = hipErrorInvalidValue;  // no kernel for the kind: validate() lets none through
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -737,7 +741,71 @@ VF_EXPORT int vf_rank_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
   return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
 }
 
-// ---- filter chains: a program of table / conv / rank / binary steps on raw frames ------------------
+// ---- colour matrix (cv2.transform) on raw 3-channel frames -----------------------------------------
+
+namespace {
+
+// The filter arguments every vf_mix_* / vf_jpeg_mix* entry point and a VF_STEP_MIX step share.
+int check_mix(vf_ctx *ctx, const char *fn, const int32_t *m, int shift, int rounding) {
+  if (!m) return set_err(ctx, VF_E_INVALID, 0, "%s: matrix is NULL", fn);
+  if (shift < 0 || shift > 16) return set_err(ctx, VF_E_INVALID, 0, "%s: shift=%d outside 0..16", fn, shift);
+  if (rounding != VF_ROUND_HALF_EVEN && rounding != VF_ROUND_HALF_UP)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: unknown rounding %d", fn, rounding);
+  for (int c = 0; c < 3; ++c) {
+    long sum = 0;
+    for (int k = 0; k < 3; ++k) {
+      const long v = m[4 * c + k];
+      if (v < -32768 || v > 32767)
+        return set_err(ctx, VF_E_INVALID, 0, "%s: weight M[%d][%d] = %ld does not fit int16", fn, c, k, v);
+      sum += std::labs(v);
+    }
+    if (sum > 65536) return set_err(ctx, VF_E_INVALID, 0, "%s: row %d: sum|M| = %ld exceeds 65536", fn, c, sum);
+    const long t = m[4 * c + 3], most = 255L << shift;
+    if (t < -most || t > most)
+      return set_err(ctx, VF_E_INVALID, 0, "%s: offset t[%d] = %ld; |t| is at most 255 * 2^shift = %ld", fn, c, t, most);
+  }
+  return VF_OK;
+}
+
+int check_mix_channels(vf_ctx *ctx, const char *fn, int channels) {
+  if (channels == 1) return set_err(ctx, VF_E_INVALID, 0, "%s: a colour matrix on 1-channel frames", fn);
+  if (channels != 3) return set_err(ctx, VF_E_INVALID, 0, "%s: channels=%d, a colour matrix takes 3", fn, channels);
+  return VF_OK;
+}
+
+}  // namespace
+
+VF_EXPORT size_t vf_mix_tile_bytes(void) { return vf::mix_tile_bytes(); }
+
+VF_EXPORT int vf_mix_device(vf_ctx *ctx, const void *dsrc, void *ddst, size_t nbytes, const int32_t *matrix, int shift,
+                            int rounding, void *stream) {
+  VF_CHECK_CTX(ctx);
+  const int rc = check_mix(ctx, "vf_mix_device", matrix, shift, rounding);
+  if (rc != VF_OK) return rc;
+  if (nbytes % 3 != 0)
+    return set_err(ctx, VF_E_INVALID, 0, "vf_mix_device: %zu bytes are not whole 3-channel pixels", nbytes);
+  if (nbytes == 0) return VF_OK;
+  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "vf_mix_device: NULL buffer");
+  if (overlaps_partially((const uint8_t *)dsrc, (const uint8_t *)ddst, nbytes))
+    return set_err(ctx, VF_E_INVALID, 0, "vf_mix_device: src and dst partially overlap");
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, vf::launch_mix(dsrc, ddst, nbytes, matrix, shift, rounding, ctx->cfg, (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_mix_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                 const int *heights, int n, int channels, const int32_t *matrix, int shift,
+                                 int rounding) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_mix_frames_host";
+  int rc = check_mix(ctx, fn, matrix, shift, rounding);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_mix_channels(ctx, fn, channels)) != VF_OK) return rc;
+  const vf_step step{VF_STEP_MIX, 0, 0, rounding, matrix, 0, 0, shift, 0, 0};  // a program of one step
+  return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
+}
+
+// ---- filter chains: a program of table / conv / rank / binary / mix steps on raw frames -------------
 
 namespace {
 
@@ -776,6 +844,11 @@ int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps,
       if ((rc = check_rank(ctx, at, in.op, e, in.kw, in.kh, in.border, &mask)) != VF_OK) return rc;
       s.kw = in.kw, s.kh = in.kh, s.border = in.border;
       s.element.assign(e, e + (size_t)in.kw * in.kh);
+    } else if (in.kind == VF_STEP_MIX) {
+      const int32_t *m = static_cast<const int32_t *>(in.data);
+      if ((rc = check_mix(ctx, at, m, in.shift, in.op)) != VF_OK) return rc;
+      s.shift = in.shift;
+      s.matrix.assign(m, m + 12);
     } else if (in.kind != VF_STEP_BINARY) {
       return set_err(ctx, VF_E_INVALID, 0, "%s: unknown kind %d", at, in.kind);
     }
@@ -1235,6 +1308,13 @@ int rank_filter(vf_ctx *ctx, const char *fn, int op, const uint8_t *element, int
   return chain_filter(ctx, fn, &step, 1, out);
 }
 
+int mix_filter(vf_ctx *ctx, const char *fn, const int32_t *matrix, int shift, int rounding, Filter *out) {
+  const int rc = check_mix(ctx, fn, matrix, shift, rounding);
+  if (rc != VF_OK) return rc;
+  const vf_step step{VF_STEP_MIX, 0, 0, rounding, matrix, 0, 0, shift, 0, 0};
+  return chain_filter(ctx, fn, &step, 1, out);
+}
+
 }  // namespace
 
 VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
@@ -1387,6 +1467,36 @@ VF_EXPORT int vf_jpeg_bench_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const
   if (const int rc = rank_filter(ctx, "vf_jpeg_bench_rank", op, element, kw, kh, border, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_rank", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms,
                            stage_ms, filter);
+}
+
+// ---- JPEG with a colour matrix in place of the inversion --------------------------------------------
+
+VF_EXPORT int vf_jpeg_mix(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                          const int32_t *matrix, int shift, int rounding, int quality, int subsamp, int flags,
+                          uint8_t *const *outs, const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = mix_filter(ctx, "vf_jpeg_mix", matrix, shift, rounding, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_mix", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
+}
+
+VF_EXPORT int vf_jpeg_mix_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                 const int32_t *matrix, int shift, int rounding, int quality, int subsamp, int flags,
+                                 uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = mix_filter(ctx, "vf_jpeg_mix_submit", matrix, shift, rounding, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_mix_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
+}
+
+VF_EXPORT int vf_jpeg_bench_mix(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                const int32_t *matrix, int shift, int rounding, int quality, int subsamp, int flags,
+                                int iters, float *ms, float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = mix_filter(ctx, "vf_jpeg_bench_mix", matrix, shift, rounding, &filter)) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_mix", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
+                           filter);
 }
 
 // ---- JPEG with a filter chain in place of the inversion ---------------------------------------------

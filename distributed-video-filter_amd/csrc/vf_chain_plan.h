@@ -30,18 +30,23 @@ namespace chain {
 constexpr int kMaxSteps = 8;  // VF_CHAIN_MAX_STEPS (include/vfilter.h)
 constexpr int kMaxSide = 7;   // the largest kernel or element side (conv::kMaxK)
 
-enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3 };                   // VF_STEP_*
+// VF_STEP_*.  The values are not dense: 4 is left out on purpose.  Kind 4 is the value the checks
+// of this file and of the C ABI have always used for "a kind that does not exist" (refused with
+// "unknown kind 4"), and callers may rely on that refusal, so the colour matrix took 5.
+enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5 };
+enum : int { kRoundHalfEven = 0, kRoundHalfUp = 1 };                             // VF_ROUND_*
 enum : int { kSubtract = 0, kAdd = 1, kAbsdiff = 2, kMin = 3, kMax = 4 };        // VF_BIN_*
 
 struct Step {
   int kind = kTable;
   int a = 0, b = 0;  // operand values; b is read by a binary step only
-  int op = 0;        // kRank: a VF_RANK_*; kBinary: a VF_BIN_*
-  int kw = 0, kh = 0, shift = 0, border = 0;  // kConv, kRank
+  int op = 0;        // kRank: a VF_RANK_*; kBinary: a VF_BIN_*; kMix: a VF_ROUND_*
+  int kw = 0, kh = 0, shift = 0, border = 0;  // kConv, kRank; shift: kMix as well
   int channels = 1;                           // kTable: 1 or 3
   std::vector<uint8_t> table;    // kTable: channels x 256, planar
   std::vector<int16_t> weights;  // kConv: kw * kh
   std::vector<uint8_t> element;  // kRank: kw * kh
+  std::vector<int32_t> matrix;   // kMix: 12, row-major [M | t] 3 x 4
 };
 
 struct Program {
@@ -70,7 +75,8 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
   for (int i = 1; i <= n; ++i) {
     const Step &s = p.steps[i - 1];
     const std::string at = "step " + std::to_string(i) + ": ";
-    if (s.kind < kTable || s.kind > kBinary) return fail(at + "unknown kind " + std::to_string(s.kind));
+    if ((s.kind < kTable || s.kind > kBinary) && s.kind != kMix)
+      return fail(at + "unknown kind " + std::to_string(s.kind));
     if (s.a < 0 || s.a >= i)
       return fail(at + "operand a = " + std::to_string(s.a) + " is not an earlier value");
     if (s.kind == kBinary) {
@@ -82,6 +88,11 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
       if (s.channels != 1 && s.channels != 3) return fail(at + "a table has 1 or 3 channels");
       if (s.table.size() != (size_t)s.channels * 256) return fail(at + "a table holds channels x 256 bytes");
       if (s.channels == 3 && frame_channels != 3) return fail(at + "a 3-channel table on 1-channel frames");
+    }
+    if (s.kind == kMix) {
+      if (frame_channels != 3) return fail(at + "a colour matrix on 1-channel frames");
+      if (s.matrix.size() != 12) return fail(at + "a colour matrix holds 3 x 4 entries");
+      if (s.op != kRoundHalfEven && s.op != kRoundHalfUp) return fail(at + "unknown rounding " + std::to_string(s.op));
     }
     if (is_neighbourhood(s)) {
       if (s.kw < 1 || s.kh < 1 || s.kw > kMaxSide || s.kh > kMaxSide || !(s.kw & 1) || !(s.kh & 1))
@@ -115,7 +126,9 @@ inline void compose_tables(const Step &first, const Step &then, Step *out) {
 }
 
 // The program with every table step whose only reader is a table step composed into that reader
-// (exact: both are per-byte maps).  The result computes the same picture in fewer steps.
+// (exact: both are per-byte maps).  The result computes the same picture in fewer steps.  Nothing
+// is composed across a colour matrix: a table beside one stays a step, and two matrices with a
+// rounding and a clamp between them are not one matrix.
 inline Program fold(const Program &in) {
   Program p = in;
   for (bool again = true; again;) {
@@ -157,8 +170,8 @@ struct Buffers {
 };
 
 // Buffers by last use.  Buffer 0 holds value 0 and is reused once value 0 is dead.  A
-// neighbourhood step never writes the buffer it reads; a table or binary step writes in place over
-// an operand that dies at that step.  Every value of a buffer sits at one row origin (the band's
+// neighbourhood step never writes the buffer it reads; a table, colour-matrix or binary step writes
+// in place over an operand that dies at that step.  Every value of a buffer sits at one row origin (the band's
 // first source row), so "in place" is dst == operand exactly.
 inline Buffers assign_buffers(const Program &p) {
   const int n = p.size();
@@ -261,9 +274,10 @@ struct Launch {
 };
 
 // The launches that make rows [y0, y1) of the result for a frame of H rows whose buffers start at
-// row s0 (the whole frame: y0 = 0, y1 = H, s0 = 0).  A table or binary step reads its operands at
-// its own first row; a neighbourhood step gets every present row of its operand.  With
-// result_to_out the last step writes row 0 of the caller's output, else its planned buffer.
+// row s0 (the whole frame: y0 = 0, y1 = H, s0 = 0).  A table, colour-matrix or binary step
+// reads its operands at its own first row; a neighbourhood step gets every present row of its
+// operand.  With result_to_out the last step writes row 0 of the caller's output, else its
+// planned buffer.
 inline std::vector<Launch> band_launches(const Program &p, const Buffers &bufs, int H, int y0, int y1, int s0,
                                          bool result_to_out) {
   const int n = p.size();

@@ -66,7 +66,18 @@ hipError_t launch_rank(const void *dsrc, void *ddst, int width, int channels, in
 hipError_t launch_binary(const void *da, const void *db, void *ddst, size_t nbytes, int op, const LaunchCfg &cfg,
                          hipStream_t stream);
 
-// The steps of a program as launches of the four kernels above (vf_api.hip): `launches` is
+// The colour matrix (vf_mix.hip; cv2.transform) over nbytes of whole 3-byte pixels
+// (nbytes % 3 == 0): dst[c] = clamp(round((sum_k m[4 c + k] * src[k] + m[4 c + 3]) / 2^shift), 0, 255).
+// m: 12 int32 in HOST memory, row-major [M | t] 3 x 4, passed on by value; every weight fits int16,
+// sum_k |M[c][k]| <= 65536, |t[c]| <= 255 * 2^shift, 0 <= shift <= 16 (the caller checks).  rounding:
+// 0 half to even, 1 (acc + 2^(shift - 1)) >> shift.  Each pointer at any alignment; ddst == dsrc
+// exactly is allowed, a partial overlap is not (the caller checks).  No device allocation;
+// asynchronous on `stream`.  mix_tile_bytes: the bytes of one workgroup's tile (a multiple of 48).
+hipError_t launch_mix(const void *dsrc, void *ddst, size_t nbytes, const int32_t m[12], int shift, int rounding,
+                      const LaunchCfg &cfg, hipStream_t stream);
+size_t mix_tile_bytes();
+
+// The steps of a program as launches of the five kernels above (vf_api.hip): `launches` is
 // vf_chain_plan.h's band_launches of a band or whole frame, masks[i] step i + 1's element when it
 // is a rank step, bufs[k] the address of buffer k's origin row (the band's row s0), out the rows a
 // chain::kOut launch writes; conv_form as launch_conv's form.

@@ -11,6 +11,9 @@ distributor.py).
                ``cv2.medianBlur`` drop-ins) and ``rank_frames``
                ``Chain`` / ``Combine`` / ``Morph`` (a program of the filters above in one GPU pass),
                ``chain``, ``chain_frames`` and ``morphology_ex`` (the ``cv2.morphologyEx`` drop-in)
+               ``transform`` (the ``cv2.transform`` drop-in: a 3 x 3 colour matrix plus offset per
+               pixel), ``Mix`` and ``transform_frames``
+  colors       builders of the usual colour matrices (gray, swap_rb, sepia, saturation, gain, ...)
   kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
   elements     builders of the usual structuring elements (rect, cross)
   _lib         ctypes binding to libvfilter_hip.so (include/vfilter.h)
@@ -18,12 +21,14 @@ distributor.py).
 The worker loop, the inverter plugin and the distributor live in ``worker``,
 ``inverter`` and ``distributor`` (imported on demand; they need no GPU to import).
 """
-from . import elements, kernels, tables  # noqa: F401
+from . import colors, elements, kernels, tables  # noqa: F401
 from ._lib import (ABI_VERSION, Context, VFilterError, device_count, get_context,  # noqa: F401
                    library_path, load_library)
-from .filters import (Chain, Combine, Morph, Rank, as_element, as_kernel, as_table, bitwise_not, chain,  # noqa: F401
+from .filters import (Chain, Combine, Mix, Morph, Rank, as_element, as_kernel, as_matrix, as_table,  # noqa: F401
+                      bitwise_not, chain,
                       chain_frames, dilate, erode, filter2d, filter2d_frames, invert, invert_batch, invert_bytes,
-                      invert_frames, lut, lut_frames, median_blur, morphology_ex, rank_frames)
+                      invert_frames, lut, lut_frames, median_blur, morphology_ex, rank_frames, transform,
+                      transform_frames)
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
@@ -31,4 +36,5 @@ __all__ = [
     "as_table", "lut", "lut_frames", "as_kernel", "filter2d", "filter2d_frames", "kernels", "tables",
     "Rank", "as_element", "erode", "dilate", "median_blur", "rank_frames", "elements",
     "Chain", "Combine", "Morph", "chain", "chain_frames", "morphology_ex",
+    "Mix", "as_matrix", "transform", "transform_frames", "colors",
 ]

@@ -115,6 +115,16 @@ SIGNATURES = {
     "vf_jpeg_bench_rank": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           _c_float_p, _c_float_p]),
+    "vf_mix_tile_bytes": (_sz, []),
+    "vf_mix_device": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "vf_mix_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                          ctypes.c_int]),
+    "vf_jpeg_mix": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_mix_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_mix": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
     "vf_binary_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
     "vf_chain_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
     "vf_jpeg_chain": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -126,7 +136,9 @@ SIGNATURES = {
 }
 
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
+STEP_MIX = 5                                                # VF_STEP_MIX: 4 names no kind and stays refused
 CHAIN_MAX_STEPS = 8                                         # VF_CHAIN_MAX_STEPS
+ROUND_HALF_EVEN, ROUND_HALF_UP = 0, 1                       # VF_ROUND_*
 
 
 class Step(ctypes.Structure):
@@ -493,10 +505,36 @@ class Context:
         self._check(self._lib.vf_rank_device(self._ctx, dsrc, ddst, width, height, channels, op, e.ctypes.data,
                                              e.shape[1], e.shape[0], border, stream or None))
 
+    # -- colour matrix (cv2.transform): vf_mix_* ------------------------------------------------------
+    @staticmethod
+    def _matrix(matrix) -> np.ndarray:
+        """``matrix`` (``filters.as_matrix``'s first result) as an array to point at."""
+        m = np.asarray(matrix)
+        if m.dtype != np.int32 or m.shape != (3, 4) or not m.flags.c_contiguous:
+            raise ValueError("matrix must be a C-contiguous 3 x 4 int32 array (see vfilter.as_matrix)")
+        return m
+
+    def mix_tile_bytes(self) -> int:
+        """The bytes of one workgroup's tile of the colour-matrix kernel."""
+        return int(self._lib.vf_mix_tile_bytes())
+
+    def mix_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                        channels: int, matrix, shift: int, rounding: int = 0) -> None:
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
+        m = self._matrix(matrix)
+        self._check(self._lib.vf_mix_frames_host(self._ctx, sa, da, wa, ha, n, channels, m.ctypes.data, shift, rounding))
+
+    def mix_device(self, dsrc: int, ddst: int, nbytes: int, matrix, shift: int, rounding: int = 0,
+                   stream: int = 0) -> None:
+        """The matrix over ``nbytes`` of device memory (whole 3-byte pixels); asynchronous."""
+        m = self._matrix(matrix)
+        self._check(self._lib.vf_mix_device(self._ctx, dsrc or None, ddst or None, nbytes, m.ctypes.data, shift,
+                                            rounding, stream or None))
+
     # -- filter chains (vf_chain_*, vf_binary_device) ------------------------------------------------
     def _steps(self, steps: Sequence):
         """``steps`` -- ``filters.Chain.args[0]``: tuples ``(kind, a, b, op, data, shift, border)`` with
-        ``data`` the planar table bytes, the int16 weights, the element or ``None`` -- as a ``vf_step``
+        ``data`` the planar table bytes, the int16 weights, the element, the int32 matrix or ``None`` -- as a ``vf_step``
         array, with the arrays it points at (keep both alive across the call)."""
         arr = (Step * max(len(steps), 1))()
         keep = []
@@ -511,6 +549,8 @@ class Context:
             elif kind == STEP_RANK:
                 d = self._element(data)
                 st.kh, st.kw = d.shape
+            elif kind == STEP_MIX:
+                d = self._matrix(data)
             else:
                 d = None
             if d is not None:
@@ -953,6 +993,38 @@ class Context:
         """``jpeg_bench_invert`` with the rank filter between the decode and the encode (its time is
         in the total, not in a stage, as ``jpeg_bench_conv``'s)."""
         return self._jpeg_bench(self._lib.vf_jpeg_bench_rank, self._element_args(op, element, border), "color",
+                                jpegs, quality, subsamp, flags, iters)
+
+    # -- JPEG with a colour matrix in place of the inversion (vf_jpeg_mix*); tickets are invert tickets ----
+    def _matrix_args(self, matrix, shift: int, rounding: int) -> tuple:
+        return self._matrix(matrix).ctypes.data_as(_vp), shift, rounding
+
+    def jpeg_mix(self, jpegs: Sequence, matrix, shift: int, rounding: int, quality: int, subsamp: int,
+                 flags: int = 0) -> list:
+        """decode -> cv2.transform -> encode for every JPEG on the GPU; returns bytes."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_mix_submit(jpegs, matrix, shift, rounding, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_mix_submit(self, jpegs: Sequence, matrix, shift: int, rounding: int, quality: int, subsamp: int,
+                        flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the matrix (copied by the library); collect with the
+        ``jpeg_invert_result*`` methods."""
+        return self._jpeg_submit("jpeg_mix_submit", self._lib.vf_jpeg_mix_submit,
+                                 self._matrix_args(matrix, shift, rounding), jpegs, None, quality, subsamp, flags)
+
+    def jpeg_mix_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, matrix, shift: int, rounding: int,
+                              quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_mix_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        return self._jpeg_submit("jpeg_mix_submit_addrs", self._lib.vf_jpeg_mix_submit,
+                                 self._matrix_args(matrix, shift, rounding), addrs, sizes, quality, subsamp, flags)
+
+    def jpeg_bench_mix(self, jpegs: Sequence, matrix, shift: int, rounding: int, quality: int, subsamp: int,
+                       flags: int = 0, iters: int = 10):
+        """``jpeg_bench_invert`` with the matrix between the decode and the encode (its time is in the
+        total, not in a stage, as ``jpeg_bench_conv``'s)."""
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_mix, self._matrix_args(matrix, shift, rounding), "color",
                                 jpegs, quality, subsamp, flags, iters)
 
     # -- JPEG with a filter chain in place of the inversion (vf_jpeg_chain*); tickets are invert tickets ----

@@ -38,6 +38,8 @@ class ChainWorker(ShapedFilterWorker):
     def frames_host(self, srcs, dsts, widths, heights, channels: int) -> None:
         if channels != 3 and self.filter.table_channels == 3:
             raise ValueError("the chain has a 3-channel table; raw frames have 3 channels")
+        if channels != 3 and self.filter.has_mix:
+            raise ValueError("the chain has a colour matrix; raw frames have 3 channels")
         self.ctx.chain_frames_host(srcs, dsts, widths, heights, channels, *self.filter.args)
 
 

@@ -440,9 +440,146 @@ def rank_frames(frames: Sequence, rank: Rank, outs: Optional[List] = None, ctx: 
                         lambda *a: (ctx or get_context()).rank_frames_host(*a, *rank.args))
 
 
+# -- colour matrix: cv2.transform --------------------------------------------------------------------
+
+ROUNDINGS = {"half_even": 0, "half_up": 1}  # VF_ROUND_* (include/vfilter.h)
+
+
+def rounding_code(rounding) -> int:
+    """``rounding`` ("half_even", cv2's float path; "half_up", ``(x + half) >> shift``, its fixed-point
+    paths) as the library's code."""
+    try:
+        return ROUNDINGS[rounding]
+    except (KeyError, TypeError):
+        raise ValueError(f"transform: rounding must be one of {sorted(ROUNDINGS)}, not {rounding!r}") from None
+
+
+def as_matrix(m) -> tuple:
+    """A ``cv2.transform`` matrix in the library's form: ``(int32 3 x 4 [M | t], shift)``, meaning
+    ``[M | t] / 2**shift``, with the smallest such shift.
+
+    ``m`` is a 3 x 3 or 3 x 4 integer array (shift 0; a 3 x 3 has offset 0), an ``(ints, shift)`` pair
+    (``vfilter.colors`` builds those), or a floating-point array that is *dyadic*: ``m * 2**s`` is
+    integral for some s in 0..16.  Every weight fits int16, ``sum|M[c]| <= 65536`` per row,
+    ``0 <= shift <= 16`` and the offsets, scaled by ``2**shift``, have ``|t[c]| <= 255 * 2**shift``.
+    Anything else -- the Rec. 601 luma as floats, a non-finite entry -- raises ``ValueError`` with the
+    reason: there is no floating-point matrix path."""
+    shift = 0
+    if isinstance(m, tuple) and len(m) == 2 and np.ndim(m[1]) == 0 and np.ndim(m[0]) == 2:
+        m, shift = m
+        if int(shift) != shift:
+            raise ValueError(f"transform: shift must be an integer, not {shift!r}")
+        shift = int(shift)
+        k = np.asarray(m)
+        if k.dtype.kind not in "iub":
+            if k.dtype.kind != "f" or not np.array_equal(k, np.rint(k)):
+                raise ValueError("transform: the entries of an (ints, shift) pair must be integers")
+    else:
+        k = np.asarray(m)
+    if k.shape not in ((3, 3), (3, 4)):
+        raise ValueError(f"transform: a matrix is 3 x 3 or 3 x 4, not shape {k.shape}")
+    if not 0 <= shift <= 16:
+        raise ValueError(f"transform: shift = {shift} outside 0..16")
+    if k.dtype.kind == "f" and not np.array_equal(k, np.rint(k)):
+        if not np.isfinite(k).all():
+            raise ValueError("transform: the matrix has a non-finite entry")
+        k = k.astype(np.float64)
+        for s in range(1, 17):
+            scaled = k * float(1 << s)  # exact: a power of two
+            if np.array_equal(scaled, np.rint(scaled)):
+                k, shift = scaled, s
+                break
+        else:
+            raise ValueError("transform: the matrix is not dyadic (no s in 0..16 makes m * 2**s integral); "
+                             "give integers and a shift")
+    elif k.dtype.kind not in "iubf":
+        raise ValueError(f"transform: a matrix of dtype {k.dtype}")
+    w = np.asarray(np.rint(k) if k.dtype.kind == "f" else k).astype(np.int64)
+    if w.shape == (3, 3):
+        w = np.concatenate([w, np.zeros((3, 1), np.int64)], axis=1)
+    while shift > 0 and not (w & 1).any():  # the smallest shift
+        w >>= 1
+        shift -= 1
+    if int(w[:, :3].max()) > 32767 or int(w[:, :3].min()) < -32768:
+        raise ValueError("transform: a weight does not fit 16 bits")
+    total = int(np.abs(w[:, :3]).sum(axis=1).max())
+    if total > 65536:
+        raise ValueError(f"transform: a row's sum|weights| = {total} exceeds 65536")
+    most = 255 << shift
+    if int(np.abs(w[:, 3]).max()) > most:
+        raise ValueError(f"transform: an offset of {int(np.abs(w[:, 3]).max())} / 2**{shift} is outside -255..255")
+    return np.ascontiguousarray(w, dtype=np.int32), shift
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Mix:
+    """``cv2.transform`` with the 3 x 3 or 3 x 4 ``matrix`` (as for ``as_matrix``) and a rounding, copied:
+    per pixel ``dst = clamp(round((M . src + t) / 2**shift))``.  ``rounding`` is "half_even" (cv2's float
+    path) or "half_up" (``(x + half) >> shift``, cv2's fixed-point paths); with shift 0 there is nothing
+    to round.  ``vfilter.colors`` builds the usual matrices.  3-channel frames only."""
+    matrix: np.ndarray  # int32 3 x 4 [M | t], read-only
+    shift: int
+    rounding: str
+    rounding_code: int
+    family = "mix"
+
+    def __init__(self, matrix, rounding: str = "half_even"):
+        if isinstance(matrix, Mix):
+            raise ValueError("Mix: matrix is a matrix or an (ints, shift) pair, not a Mix")
+        code = rounding_code(rounding)
+        m, shift = as_matrix(matrix)
+        m.flags.writeable = False
+        for name, v in (("matrix", m), ("shift", shift), ("rounding", rounding), ("rounding_code", code)):
+            object.__setattr__(self, name, v)
+
+    @property
+    def args(self) -> tuple:
+        return self.matrix, self.shift, self.rounding_code
+
+
+def _as_mix(name: str, m, rounding: str) -> Mix:
+    if not isinstance(m, Mix):
+        return Mix(m, rounding)
+    if rounding not in ("half_even", m.rounding):  # the default leaves a Mix its own rounding
+        raise ValueError(f"{name}: the Mix rounds {m.rounding}; rounding={rounding!r} contradicts it")
+    return m
+
+
+def _mix_frame(name: str, a) -> np.ndarray:
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+        raise ValueError(f"{name}: frames must be uint8 ndarrays")
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"{name}: a colour matrix mixes the 3 channels of a pixel; frames are H x W x 3, "
+                         f"not shape {a.shape}")
+    return a
+
+
+def transform(src: np.ndarray, m, dst: Optional[np.ndarray] = None, rounding: str = "half_even",
+              ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.transform(src, m)`` on uint8 ``H x W x 3`` input with a 3 x 3 or 3 x 4 ``m`` that
+    ``as_matrix`` accepts (or a ``Mix``, which carries its rounding), exact in integers: grayscale
+    kept in 3 channels, BGR <-> RGB, sepia, saturation, white balance, channel mixing
+    (``vfilter.colors``).  ``dst`` as for ``lut``, and it may be ``src``.  1-channel frames are refused."""
+    mix = _as_mix("transform", m, rounding)
+    src = np.ascontiguousarray(_mix_frame("transform", src))
+    dst = _rank_dst("transform", src, dst)
+    if src.size:
+        (ctx or get_context()).mix_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], 3, *mix.args)
+    return dst
+
+
+def transform_frames(frames: Sequence, mix, outs: Optional[List] = None, ctx: Optional[Context] = None) -> List:
+    """A ``Mix`` (or a matrix, as for ``transform``) over separately stored ``H x W x 3`` frames of mixed
+    sizes in one call.  Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
+    mix = _as_mix("transform_frames", mix, "half_even")
+    return _frames_call("transform_frames", [_mix_frame("transform_frames", f) for f in frames], outs,
+                        lambda *a: (ctx or get_context()).mix_frames_host(*a, *mix.args))
+
+
 # -- filter chains: a program of filters between one upload and one download ----------------------
 
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
+STEP_MIX = 5  # VF_STEP_MIX: 4 names no kind and stays refused
 BINARY_OPS = {"subtract": 0, "add": 1, "absdiff": 2, "min": 3, "max": 4}  # VF_BIN_*
 CHAIN_MAX_STEPS = 8  # VF_CHAIN_MAX_STEPS
 MORPH_OPS = ("erode", "dilate", "open", "close", "gradient", "tophat", "blackhat")
@@ -482,7 +619,9 @@ def _unary_step(f, a: int) -> tuple:
         return (STEP_CONV, a, 0, 0, f.weights, f.shift, f.border_code)
     if isinstance(f, Rank):
         return (STEP_RANK, a, 0, f.op_code, f.element, 0, f.border_code)
-    raise ValueError(f"chain: a step is Invert, Table, Kernel, Rank, Combine or Chain, not {type(f).__name__}")
+    if isinstance(f, Mix):
+        return (STEP_MIX, a, 0, f.rounding_code, f.matrix, f.shift, 0)
+    raise ValueError(f"chain: a step is Invert, Table, Kernel, Rank, Mix, Combine or Chain, not {type(f).__name__}")
 
 
 def _check_program(steps: Sequence[tuple]) -> None:
@@ -558,11 +697,16 @@ class Chain:
         """3 when a step is a 3-channel table (such a chain takes 3-channel frames only), else 1."""
         return 3 if any(st[0] == STEP_TABLE and len(st[4]) == 768 for st in self.steps) else 1
 
+    @property
+    def has_mix(self) -> bool:
+        """True when a step is a colour matrix (such a chain takes 3-channel frames only)."""
+        return any(st[0] == STEP_MIX for st in self.steps)
+
     def __len__(self) -> int:
         return len(self.steps)
 
 
-_CHAIN_ITEMS = (Invert, Table, Kernel, Rank)
+_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix)
 
 
 def _lower(item, cur: int, prog: List[tuple]) -> int:
@@ -626,6 +770,8 @@ def _chain_frame(name: str, a, c: Chain) -> np.ndarray:
     a = _conv_frame(name, a)
     if c.table_channels == 3 and (a.ndim != 3 or a.shape[2] != 3):
         raise ValueError(f"{name}: the chain has a 3-channel table; frames are H x W x 3, not shape {a.shape}")
+    if c.has_mix and (a.ndim != 3 or a.shape[2] != 3):
+        raise ValueError(f"{name}: the chain has a colour matrix; frames are H x W x 3, not shape {a.shape}")
     return a
 
 

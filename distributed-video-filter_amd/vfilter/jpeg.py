@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import Invert, Kernel, Morph, Rank, Table, _as_chain
+from .filters import Invert, Kernel, Morph, Rank, Table, _as_chain, _as_mix
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -205,6 +205,19 @@ class TurboJPEG:
     def median_blur_batch(self, jpeg_bufs: Sequence, ksize: int, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
                           flags: int = 0) -> List[bytes]:
         return self.filter_batch(jpeg_bufs, Rank.median(ksize), quality, jpeg_subsample, flags)
+
+    # -- a colour matrix: cv2.transform between decode and encode ---------------------------------------
+    # The submit forms go through ``filter_batch_submit*`` with a ``vfilter.filters.Mix``.
+    def transform(self, jpeg_buf, m, rounding: str = "half_even", quality: int = 85,
+                  jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(cv2.transform(decode(jpeg_buf), m))`` on the GPU, the pixels never leaving it.  ``m``
+        and ``rounding`` as for ``vfilter.transform``; the matrix sees the decoded BGR pixel (channel 0
+        is blue)."""
+        return self.filter_batch([jpeg_buf], _as_mix("transform", m, rounding), quality, jpeg_subsample, flags)[0]
+
+    def transform_batch(self, jpeg_bufs: Sequence, m, rounding: str = "half_even", quality: int = 85,
+                        jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, _as_mix("transform_batch", m, rounding), quality, jpeg_subsample, flags)
 
     # -- a filter chain (vfilter.filters.Chain) between one decode and one encode ------------------------
     def chain(self, jpeg_buf, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:

@@ -426,6 +426,54 @@ int vf_jpeg_bench_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
                        int op, const uint8_t *element, int kw, int kh, int border, int quality,
                        int subsamp, int flags, int iters, float *ms, float *stage_ms);
 
+/* ---- colour matrix (cv2.transform: grayscale, BGR <-> RGB, sepia, saturation, ...) -----------
+ * For uint8 frames of 3 interleaved channels, exact in integers.  `matrix` is a
+ * HOST pointer to 12 int32, row-major [M | t] 3 x 4, read during the call only:
+ *   acc[c] = sum_k M[c][k] * src[k] + t[c]          c, k in {0, 1, 2}
+ *   q      = acc                                     when shift == 0, else acc / 2^shift rounded:
+ *              VF_ROUND_HALF_EVEN  to nearest, a tie to the even integer
+ *              VF_ROUND_HALF_UP    (acc + 2^(shift - 1)) >> shift, the shift arithmetic
+ *   dst[c] = min(max(q, 0), 255)
+ * Every M[c][k] fits int16, sum_k |M[c][k]| <= 65536 per row, 0 <= shift <= 16 and t[c], already
+ * scaled by 2^shift, has |t[c]| <= 255 * 2^shift.  Anything else, a NULL `matrix`, an unknown
+ * rounding, or 1-channel frames is VF_E_INVALID. */
+#define VF_ROUND_HALF_EVEN 0
+#define VF_ROUND_HALF_UP   1
+
+/* The bytes of one workgroup's tile of the colour-matrix kernel (a multiple of 48).  Makes no
+ * HIP call. */
+size_t vf_mix_tile_bytes(void);
+
+/* Enqueue the matrix on `stream` over nbytes of device memory, whole 3-byte pixels
+ * (nbytes % 3 == 0).  Returns after the launch (does not synchronise); any alignment.  ddst ==
+ * dsrc exactly is allowed; a partial overlap is VF_E_INVALID.  nbytes == 0 writes nothing. */
+int vf_mix_device(vf_ctx *ctx, const void *dsrc, void *ddst, size_t nbytes, const int32_t *matrix,
+                  int shift, int rounding, void *stream);
+
+/* The matrix on `n` separately allocated host frames (srcs[i] -> dsts[i], widths[i] x heights[i]
+ * x channels, channels == 3), synchronous, as vf_conv_frames_host: srcs[i] == dsts[i] is allowed;
+ * a frame larger than the context's staging is cut into bands of rows. */
+int vf_mix_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                       const int *widths, const int *heights, int n, int channels,
+                       const int32_t *matrix, int shift, int rounding);
+
+/* vf_jpeg_invert with the matrix in place of the inversion: decode -> matrix -> encode on the
+ * GPU, on the pixels of the decoded BGR frame (channel 0 is blue). */
+int vf_jpeg_mix(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                const int32_t *matrix, int shift, int rounding, int quality, int subsamp, int flags,
+                uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the matrix (copied).  The ticket is an invert ticket: collect with
+ * vf_jpeg_invert_query / _wait / _fetch / _scatter. */
+int vf_jpeg_mix_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                       const int32_t *matrix, int shift, int rounding, int quality, int subsamp,
+                       int flags, uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the matrix between the decode and the encode. */
+int vf_jpeg_bench_mix(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                      const int32_t *matrix, int shift, int rounding, int quality, int subsamp,
+                      int flags, int iters, float *ms, float *stage_ms);
+
 /* ---- filter chains (cv2.morphologyEx, difference of blurs, ...) -----------------------------
  * A program is a straight-line list of 1 .. VF_CHAIN_MAX_STEPS steps over values.
  * Value 0 is the input frame (uint8, 1 or 3 interleaved channels, packed rows), value i the result
@@ -439,14 +487,19 @@ int vf_jpeg_bench_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
  *   VF_STEP_BINARY  `op` a VF_BIN_*, per byte on the values `a` and `b`:
  *                   SUBTRACT max(a - b, 0), ADD min(a + b, 255), ABSDIFF |a - b|, MIN, MAX
  *                   (cv2.subtract, cv2.add, cv2.absdiff, cv2.min, cv2.max on uint8)
+ *   VF_STEP_MIX     cv2.transform: `data` is the 12 int32 [M | t] of vf_mix_*, with `shift`, and
+ *                   `op` a VF_ROUND_*; 3-channel frames only
  * `data` is a HOST pointer, read during the call only.  VF_E_INVALID, before any GPU work: a step
  * that reads a later value or itself, a value other than the last that no step reads, a 3-channel
- * table on 1-channel frames, more than VF_CHAIN_MAX_STEPS steps, and anything the single-filter
- * entry points refuse for a table, a kernel or an element. */
+ * table or a colour matrix on 1-channel frames, more than VF_CHAIN_MAX_STEPS steps, and anything
+ * the single-filter entry points refuse for a table, a kernel, an element or a matrix.
+ * The VF_STEP_* values are not dense: 4 names no kind and stays refused ("unknown kind 4"), as
+ * callers' checks of the refusal expect, so VF_STEP_MIX is 5. */
 #define VF_STEP_TABLE  0
 #define VF_STEP_CONV   1
 #define VF_STEP_RANK   2
 #define VF_STEP_BINARY 3
+#define VF_STEP_MIX    5
 #define VF_BIN_SUBTRACT 0
 #define VF_BIN_ADD      1
 #define VF_BIN_ABSDIFF  2
@@ -457,10 +510,10 @@ int vf_jpeg_bench_rank(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
 typedef struct vf_step {
   int kind;         /* a VF_STEP_* */
   int a, b;         /* operand values; b for VF_STEP_BINARY only */
-  int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_* */
-  const void *data; /* the table, the int16 weights or the element (host memory) */
+  int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_*; VF_STEP_MIX: a VF_ROUND_* */
+  const void *data; /* the table, the int16 weights, the element or the 12 int32 (host memory) */
   int kw, kh;       /* VF_STEP_CONV, VF_STEP_RANK */
-  int shift;        /* VF_STEP_CONV */
+  int shift;        /* VF_STEP_CONV, VF_STEP_MIX */
   int border;       /* VF_STEP_CONV, VF_STEP_RANK: a VF_BORDER_* */
   int channels;     /* VF_STEP_TABLE: 1 or 3 */
 } vf_step;
