@@ -32,6 +32,7 @@
 #include "vf_env.h"
 #include "vf_host_mem.h"
 #include "vf_internal.h"
+#include "vf_sep_plan.h"
 #include "vf_jpeg_codec.h"
 #include "vf_lut_split.h"
 #include "vf_conv_bands.h"
@@ -561,6 +562,9 @@ hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const
                       s.border, stream);
     else if (s.kind == chain::kMix)
       e = launch_mix(a, dst, nbytes, s.matrix.data(), s.shift, s.op, cfg, stream);
+    else if (s.kind == chain::kSep)
+      e = launch_sep(a, dst, w, channels, frame_h, l.y0, l.nrows, l.src0, l.nsrc, s.taps_x.data(), s.kw, s.taps_y.data(),
+                     s.kh, s.shift, s.divisor, s.op, s.border, sep_form_env(), stream);
     else
       e = hipErrorInvalidValue;  // no kernel for the kind: validate() lets none through
     if (e != hipSuccess) return e;
@@ -805,7 +809,64 @@ VF_EXPORT int vf_mix_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_
   return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
 }
 
-// ---- filter chains: a program of table / conv / rank / binary / mix steps on raw frames -------------
+// ---- separable filter (cv2.sepFilter2D, cv2.blur, cv2.boxFilter) on raw frames ---------------------
+
+namespace {
+
+// The filter arguments every vf_sep_* / vf_jpeg_sep* entry point and a VF_STEP_SEP step share
+// (vf_sep_plan.h has the limits).
+int check_sep(vf_ctx *ctx, const char *fn, const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor,
+              int rounding, int border) {
+  std::string why;
+  if (!vf::sep::limits_ok(kx, kw, ky, kh, shift, divisor, rounding, border, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  return VF_OK;
+}
+
+// A VF_STEP_SEP step's data for the taps of an entry point: the divisor, kx, ky as int32.
+std::vector<int32_t> sep_step_data(const int16_t *kx, int kw, const int16_t *ky, int kh, int divisor) {
+  std::vector<int32_t> d{divisor};
+  d.insert(d.end(), kx, kx + kw);
+  d.insert(d.end(), ky, ky + kh);
+  return d;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_sep_tile(int kw, int kh, int *row_bytes, int *rows) {
+  if (!vf::sep::side_ok(kw) || !vf::sep::side_ok(kh) || !row_bytes || !rows) return VF_E_INVALID;
+  *row_bytes = vf::sep::kTileBytes;
+  *rows = vf::sep_tile_rows(kh);
+  return VF_OK;
+}
+
+VF_EXPORT int vf_sep_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                            const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor, int rounding,
+                            int border, void *stream) {
+  VF_CHECK_CTX(ctx);
+  int rc = check_sep(ctx, "vf_sep_device", kx, kw, ky, kh, shift, divisor, rounding, border);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_device_frame(ctx, "vf_sep_device", dsrc, ddst, width, height, channels)) != VF_OK)
+    return rc < 0 ? rc : VF_OK;
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, vf::launch_sep(dsrc, ddst, width, channels, height, 0, height, 0, height, kx, kw, ky, kh, shift, divisor,
+                             rounding, border, vf::sep_form_env(), (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_sep_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                 const int *heights, int n, int channels, const int16_t *kx, int kw, const int16_t *ky,
+                                 int kh, int shift, int divisor, int rounding, int border) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_sep_frames_host";
+  const int rc = check_sep(ctx, fn, kx, kw, ky, kh, shift, divisor, rounding, border);
+  if (rc != VF_OK) return rc;
+  const std::vector<int32_t> data = sep_step_data(kx, kw, ky, kh, divisor);
+  const vf_step step{VF_STEP_SEP, 0, 0, rounding, data.data(), kw, kh, shift, border, 0};  // a program of one step
+  return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
+}
+
+// ---- filter chains: a program of table / conv / rank / binary / mix / sep steps on raw frames -------
 
 namespace {
 
@@ -849,6 +910,23 @@ int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps,
       if ((rc = check_mix(ctx, at, m, in.shift, in.op)) != VF_OK) return rc;
       s.shift = in.shift;
       s.matrix.assign(m, m + 12);
+    } else if (in.kind == VF_STEP_SEP) {
+      // data: the divisor (0 or 1: none), kw horizontal taps, kh vertical taps, int32 each
+      const int32_t *d = static_cast<const int32_t *>(in.data);
+      if (!d) return set_err(ctx, VF_E_INVALID, 0, "%s: taps are NULL", at);
+      if (!vf::sep::side_ok(in.kw) || !vf::sep::side_ok(in.kh))
+        return set_err(ctx, VF_E_INVALID, 0, "%s: a %d x %d separable kernel; tap counts are odd and at most %d", at, in.kw,
+                       in.kh, vf::sep::kMaxSide);
+      for (int k = 1; k <= in.kw + in.kh; ++k)
+        if (d[k] < -32768 || d[k] > 32767)
+          return set_err(ctx, VF_E_INVALID, 0, "%s: tap %d = %d does not fit int16", at, k - 1, d[k]);
+      s.taps_x.assign(d + 1, d + 1 + in.kw);
+      s.taps_y.assign(d + 1 + in.kw, d + 1 + in.kw + in.kh);
+      s.divisor = d[0] == 0 ? 1 : d[0];
+      if ((rc = check_sep(ctx, at, s.taps_x.data(), in.kw, s.taps_y.data(), in.kh, in.shift, s.divisor, in.op,
+                          in.border)) != VF_OK)
+        return rc;
+      s.kw = in.kw, s.kh = in.kh, s.shift = in.shift, s.border = in.border;
     } else if (in.kind != VF_STEP_BINARY) {
       return set_err(ctx, VF_E_INVALID, 0, "%s: unknown kind %d", at, in.kind);
     }
@@ -1315,6 +1393,15 @@ int mix_filter(vf_ctx *ctx, const char *fn, const int32_t *matrix, int shift, in
   return chain_filter(ctx, fn, &step, 1, out);
 }
 
+int sep_filter(vf_ctx *ctx, const char *fn, const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor,
+               int rounding, int border, Filter *out) {
+  const int rc = check_sep(ctx, fn, kx, kw, ky, kh, shift, divisor, rounding, border);
+  if (rc != VF_OK) return rc;
+  const std::vector<int32_t> data = sep_step_data(kx, kw, ky, kh, divisor);
+  const vf_step step{VF_STEP_SEP, 0, 0, rounding, data.data(), kw, kh, shift, border, 0};
+  return chain_filter(ctx, fn, &step, 1, out);
+}
+
 }  // namespace
 
 VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
@@ -1496,6 +1583,39 @@ VF_EXPORT int vf_jpeg_bench_mix(vf_ctx *ctx, const uint8_t *const *jpegs, const 
   Filter filter;
   if (const int rc = mix_filter(ctx, "vf_jpeg_bench_mix", matrix, shift, rounding, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_mix", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
+                           filter);
+}
+
+// ---- JPEG with a separable filter in place of the inversion ------------------------------------------
+
+VF_EXPORT int vf_jpeg_sep(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, const int16_t *kx,
+                          int kw, const int16_t *ky, int kh, int shift, int divisor, int rounding, int border,
+                          int quality, int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = sep_filter(ctx, "vf_jpeg_sep", kx, kw, ky, kh, shift, divisor, rounding, border, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_sep", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
+}
+
+VF_EXPORT int vf_jpeg_sep_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                 const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor,
+                                 int rounding, int border, int quality, int subsamp, int flags, uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = sep_filter(ctx, "vf_jpeg_sep_submit", kx, kw, ky, kh, shift, divisor, rounding, border, &filter))
+    return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_sep_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
+}
+
+VF_EXPORT int vf_jpeg_bench_sep(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                                const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor,
+                                int rounding, int border, int quality, int subsamp, int flags, int iters, float *ms,
+                                float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = sep_filter(ctx, "vf_jpeg_bench_sep", kx, kw, ky, kh, shift, divisor, rounding, border, &filter))
+    return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_sep", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
                            filter);
 }
 

@@ -29,24 +29,28 @@ namespace chain {
 
 constexpr int kMaxSteps = 8;  // VF_CHAIN_MAX_STEPS (include/vfilter.h)
 constexpr int kMaxSide = 7;   // the largest kernel or element side (conv::kMaxK)
+constexpr int kMaxSepSide = 31;  // the most taps of one axis of a separable step (sep::kMaxSide)
 
 // VF_STEP_*.  The values are not dense: 4 is left out on purpose.  Kind 4 is the value the checks
 // of this file and of the C ABI have always used for "a kind that does not exist" (refused with
-// "unknown kind 4"), and callers may rely on that refusal, so the colour matrix took 5.
-enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5 };
+// "unknown kind 4"), and callers may rely on that refusal, so the colour matrix took 5.  6 and 9
+// are refused in callers' checks the same way, so the separable filter took 7.
+enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5, kSep = 7 };
 enum : int { kRoundHalfEven = 0, kRoundHalfUp = 1 };                             // VF_ROUND_*
 enum : int { kSubtract = 0, kAdd = 1, kAbsdiff = 2, kMin = 3, kMax = 4 };        // VF_BIN_*
 
 struct Step {
   int kind = kTable;
   int a = 0, b = 0;  // operand values; b is read by a binary step only
-  int op = 0;        // kRank: a VF_RANK_*; kBinary: a VF_BIN_*; kMix: a VF_ROUND_*
-  int kw = 0, kh = 0, shift = 0, border = 0;  // kConv, kRank; shift: kMix as well
+  int op = 0;        // kRank: a VF_RANK_*; kBinary: a VF_BIN_*; kMix, kSep: a VF_ROUND_*
+  int kw = 0, kh = 0, shift = 0, border = 0;  // kConv, kRank, kSep; shift: kMix as well
   int channels = 1;                           // kTable: 1 or 3
   std::vector<uint8_t> table;    // kTable: channels x 256, planar
   std::vector<int16_t> weights;  // kConv: kw * kh
   std::vector<uint8_t> element;  // kRank: kw * kh
   std::vector<int32_t> matrix;   // kMix: 12, row-major [M | t] 3 x 4
+  std::vector<int16_t> taps_x, taps_y;  // kSep: kw horizontal and kh vertical taps
+  int divisor = 1;                      // kSep: odd, 1 .. 1023; 1: none
 };
 
 struct Program {
@@ -54,7 +58,7 @@ struct Program {
   int size() const { return (int)steps.size(); }
 };
 
-inline bool is_neighbourhood(const Step &s) { return s.kind == kConv || s.kind == kRank; }
+inline bool is_neighbourhood(const Step &s) { return s.kind == kConv || s.kind == kRank || s.kind == kSep; }
 inline int radius(const Step &s) { return is_neighbourhood(s) ? s.kh / 2 : 0; }  // vertical
 
 // Is value v read by step s?
@@ -75,7 +79,7 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
   for (int i = 1; i <= n; ++i) {
     const Step &s = p.steps[i - 1];
     const std::string at = "step " + std::to_string(i) + ": ";
-    if ((s.kind < kTable || s.kind > kBinary) && s.kind != kMix)
+    if ((s.kind < kTable || s.kind > kBinary) && s.kind != kMix && s.kind != kSep)
       return fail(at + "unknown kind " + std::to_string(s.kind));
     if (s.a < 0 || s.a >= i)
       return fail(at + "operand a = " + std::to_string(s.a) + " is not an earlier value");
@@ -94,7 +98,13 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
       if (s.matrix.size() != 12) return fail(at + "a colour matrix holds 3 x 4 entries");
       if (s.op != kRoundHalfEven && s.op != kRoundHalfUp) return fail(at + "unknown rounding " + std::to_string(s.op));
     }
-    if (is_neighbourhood(s)) {
+    if (s.kind == kSep) {
+      if (s.kw < 1 || s.kh < 1 || s.kw > kMaxSepSide || s.kh > kMaxSepSide || !(s.kw & 1) || !(s.kh & 1))
+        return fail(at + "a separable step's tap counts are odd and at most " + std::to_string(kMaxSepSide));
+      if (s.taps_x.size() != (size_t)s.kw || s.taps_y.size() != (size_t)s.kh)
+        return fail(at + "the taps do not hold kw and kh entries");
+      if (s.op != kRoundHalfEven && s.op != kRoundHalfUp) return fail(at + "unknown rounding " + std::to_string(s.op));
+    } else if (is_neighbourhood(s)) {
       if (s.kw < 1 || s.kh < 1 || s.kw > kMaxSide || s.kh > kMaxSide || !(s.kw & 1) || !(s.kh & 1))
         return fail(at + "sides are odd and at most " + std::to_string(kMaxSide));
       const size_t count = (size_t)s.kw * (size_t)s.kh;
@@ -128,7 +138,8 @@ inline void compose_tables(const Step &first, const Step &then, Step *out) {
 // The program with every table step whose only reader is a table step composed into that reader
 // (exact: both are per-byte maps).  The result computes the same picture in fewer steps.  Nothing
 // is composed across a colour matrix: a table beside one stays a step, and two matrices with a
-// rounding and a clamp between them are not one matrix.
+// rounding and a clamp between them are not one matrix.  Nor across a separable step: only table
+// steps are ever composed.
 inline Program fold(const Program &in) {
   Program p = in;
   for (bool again = true; again;) {
@@ -171,7 +182,8 @@ struct Buffers {
 
 // Buffers by last use.  Buffer 0 holds value 0 and is reused once value 0 is dead.  A
 // neighbourhood step never writes the buffer it reads; a table, colour-matrix or binary step writes
-// in place over an operand that dies at that step.  Every value of a buffer sits at one row origin (the band's
+// in place over an operand that dies at that step (a separable step is a neighbourhood step: never
+// in place).  Every value of a buffer sits at one row origin (the band's
 // first source row), so "in place" is dst == operand exactly.
 inline Buffers assign_buffers(const Program &p) {
   const int n = p.size();

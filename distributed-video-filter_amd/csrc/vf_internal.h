@@ -77,7 +77,22 @@ hipError_t launch_mix(const void *dsrc, void *ddst, size_t nbytes, const int32_t
                       const LaunchCfg &cfg, hipStream_t stream);
 size_t mix_tile_bytes();
 
-// The steps of a program as launches of the five kernels above (vf_api.hip): `launches` is
+// The separable filter (vf_sep.hip; cv2.sepFilter2D, cv2.blur, cv2.boxFilter), out of
+// place, with launch_conv's geometry and row arguments (frame_h, output rows, source rows: bands
+// work the same way).  kx: kw horizontal taps, ky: kh vertical taps, int16 in HOST memory, passed on
+// by value; odd counts of at most 31, sum|kx| * sum|ky| <= 65536.  The exact 32-bit sum is divided
+// by 2^shift (rounding: 0 half to even, 1 (acc + 2^(shift - 1)) >> shift) or, with shift 0, by the
+// odd divisor (1: none; to nearest, no tie exists), then clamped (vf_sep_plan.h's limits_ok).
+// form: 0 16-bit vertical sums where they hold, 1 always 32-bit (sep_form_env reads VF_SEP_FORM =
+// wide).  sep_tile_rows: the rows of the kernel's tile for kh vertical taps (VF_SEP_ROWS overrides
+// the plan's choice for a measurement).  No device allocation; asynchronous on `stream`.
+hipError_t launch_sep(const void *dsrc, void *ddst, int width, int channels, int frame_h, int y0, int nrows, int s0,
+                      int nsrc, const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor,
+                      int rounding, int border, int form, hipStream_t stream);
+int sep_form_env();
+int sep_tile_rows(int kh);
+
+// The steps of a program as launches of the six kernels above (vf_api.hip): `launches` is
 // vf_chain_plan.h's band_launches of a band or whole frame, masks[i] step i + 1's element when it
 // is a rank step, bufs[k] the address of buffer k's origin row (the band's row s0), out the rows a
 // chain::kOut launch writes; conv_form as launch_conv's form.

@@ -13,6 +13,9 @@ distributor.py).
                ``chain``, ``chain_frames`` and ``morphology_ex`` (the ``cv2.morphologyEx`` drop-in)
                ``transform`` (the ``cv2.transform`` drop-in: a 3 x 3 colour matrix plus offset per
                pixel), ``Mix`` and ``transform_frames``
+               ``sep_filter2d``, ``blur`` and ``box_filter`` (the ``cv2.sepFilter2D``, ``cv2.blur`` and
+               ``cv2.boxFilter`` drop-ins: up to 31 taps an axis, the mean by an exact division),
+               ``Separable`` and ``sep_frames``
   colors       builders of the usual colour matrices (gray, swap_rb, sepia, saturation, gain, ...)
   kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
   elements     builders of the usual structuring elements (rect, cross)
@@ -29,6 +32,7 @@ from .filters import (Chain, Combine, Mix, Morph, Rank, as_element, as_kernel, a
                       chain_frames, dilate, erode, filter2d, filter2d_frames, invert, invert_batch, invert_bytes,
                       invert_frames, lut, lut_frames, median_blur, morphology_ex, rank_frames, transform,
                       transform_frames)
+from .filters import Separable, as_taps, blur, box_filter, sep_filter2d, sep_frames  # noqa: F401
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
@@ -37,4 +41,5 @@ __all__ = [
     "Rank", "as_element", "erode", "dilate", "median_blur", "rank_frames", "elements",
     "Chain", "Combine", "Morph", "chain", "chain_frames", "morphology_ex",
     "Mix", "as_matrix", "transform", "transform_frames", "colors",
+    "Separable", "as_taps", "sep_filter2d", "blur", "box_filter", "sep_frames",
 ]

@@ -125,6 +125,20 @@ SIGNATURES = {
                                           ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "vf_jpeg_bench_mix": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
+    "vf_sep_tile": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p]),
+    "vf_sep_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "vf_sep_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vf_jpeg_sep": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   _vp, _vp, _vp]),
+    "vf_jpeg_sep_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_sep": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
     "vf_binary_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
     "vf_chain_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
     "vf_jpeg_chain": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -137,6 +151,7 @@ SIGNATURES = {
 
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
 STEP_MIX = 5                                                # VF_STEP_MIX: 4 names no kind and stays refused
+STEP_SEP = 7                                                # VF_STEP_SEP: 6 stays refused as well
 CHAIN_MAX_STEPS = 8                                         # VF_CHAIN_MAX_STEPS
 ROUND_HALF_EVEN, ROUND_HALF_UP = 0, 1                       # VF_ROUND_*
 
@@ -531,6 +546,36 @@ class Context:
         self._check(self._lib.vf_mix_device(self._ctx, dsrc or None, ddst or None, nbytes, m.ctypes.data, shift,
                                             rounding, stream or None))
 
+    # -- separable filter (cv2.sepFilter2D, cv2.blur, cv2.boxFilter): vf_sep_* ------------------------------
+    @staticmethod
+    def _taps(taps) -> np.ndarray:
+        """``taps`` (``filters.as_taps``'s first result) as an array to point at."""
+        t = np.asarray(taps)
+        if t.dtype != np.int16 or t.ndim != 1 or not t.flags.c_contiguous:
+            raise ValueError("taps must be a C-contiguous 1-D int16 array (see vfilter.as_taps)")
+        return t
+
+    def sep_tile(self, kw: int, kh: int) -> tuple:
+        """``(row_bytes, rows)`` of one workgroup's output tile of the separable kernel for kw x kh taps."""
+        rb, rows = ctypes.c_int(0), ctypes.c_int(0)
+        if self._lib.vf_sep_tile(kw, kh, ctypes.byref(rb), ctypes.byref(rows)) != 0:
+            raise ValueError(f"sep_tile: tap counts {kw} x {kh}; they are odd and at most 31")
+        return rb.value, rows.value
+
+    def sep_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                        channels: int, kx, ky, shift: int = 0, divisor: int = 1, rounding: int = 0,
+                        border: int = 0) -> None:
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
+        x, y = self._taps(kx), self._taps(ky)
+        self._check(self._lib.vf_sep_frames_host(self._ctx, sa, da, wa, ha, n, channels, x.ctypes.data, x.size,
+                                                 y.ctypes.data, y.size, shift, divisor, rounding, border))
+
+    def sep_device(self, dsrc: int, ddst: int, width: int, height: int, channels: int, kx, ky, shift: int = 0,
+                   divisor: int = 1, rounding: int = 0, border: int = 0, stream: int = 0) -> None:
+        x, y = self._taps(kx), self._taps(ky)
+        self._check(self._lib.vf_sep_device(self._ctx, dsrc, ddst, width, height, channels, x.ctypes.data, x.size,
+                                            y.ctypes.data, y.size, shift, divisor, rounding, border, stream or None))
+
     # -- filter chains (vf_chain_*, vf_binary_device) ------------------------------------------------
     def _steps(self, steps: Sequence):
         """``steps`` -- ``filters.Chain.args[0]``: tuples ``(kind, a, b, op, data, shift, border)`` with
@@ -551,6 +596,10 @@ class Context:
                 st.kh, st.kw = d.shape
             elif kind == STEP_MIX:
                 d = self._matrix(data)
+            elif kind == STEP_SEP:  # data: (kx, ky, divisor) -> the divisor, kx, ky as int32
+                kx, ky, divisor = data
+                st.kw, st.kh = len(kx), len(ky)
+                d = np.concatenate([[divisor], self._taps(kx), self._taps(ky)]).astype(np.int32)
             else:
                 d = None
             if d is not None:
@@ -1026,6 +1075,41 @@ class Context:
         total, not in a stage, as ``jpeg_bench_conv``'s)."""
         return self._jpeg_bench(self._lib.vf_jpeg_bench_mix, self._matrix_args(matrix, shift, rounding), "color",
                                 jpegs, quality, subsamp, flags, iters)
+
+    # -- JPEG with a separable filter in place of the inversion (vf_jpeg_sep*); tickets are invert tickets ----
+    def _taps_args(self, kx, ky, shift: int, divisor: int, rounding: int, border: int) -> tuple:
+        x, y = self._taps(kx), self._taps(ky)
+        return x.ctypes.data_as(_vp), x.size, y.ctypes.data_as(_vp), y.size, shift, divisor, rounding, border
+
+    def jpeg_sep(self, jpegs: Sequence, kx, ky, shift: int, divisor: int, rounding: int, border: int, quality: int,
+                 subsamp: int, flags: int = 0) -> list:
+        """decode -> cv2.sepFilter2D / cv2.blur -> encode for every JPEG on the GPU; returns bytes."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_sep_submit(jpegs, kx, ky, shift, divisor, rounding, border, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_sep_submit(self, jpegs: Sequence, kx, ky, shift: int, divisor: int, rounding: int, border: int,
+                        quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the taps (copied by the library); collect with the
+        ``jpeg_invert_result*`` methods."""
+        return self._jpeg_submit("jpeg_sep_submit", self._lib.vf_jpeg_sep_submit,
+                                 self._taps_args(kx, ky, shift, divisor, rounding, border), jpegs, None, quality,
+                                 subsamp, flags)
+
+    def jpeg_sep_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, kx, ky, shift: int, divisor: int,
+                              rounding: int, border: int, quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_sep_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        return self._jpeg_submit("jpeg_sep_submit_addrs", self._lib.vf_jpeg_sep_submit,
+                                 self._taps_args(kx, ky, shift, divisor, rounding, border), addrs, sizes, quality,
+                                 subsamp, flags)
+
+    def jpeg_bench_sep(self, jpegs: Sequence, kx, ky, shift: int, divisor: int, rounding: int, border: int,
+                       quality: int, subsamp: int, flags: int = 0, iters: int = 10):
+        """``jpeg_bench_invert`` with the separable filter between the decode and the encode (its time is in
+        the total, not in a stage, as ``jpeg_bench_conv``'s)."""
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_sep, self._taps_args(kx, ky, shift, divisor, rounding, border),
+                                "color", jpegs, quality, subsamp, flags, iters)
 
     # -- JPEG with a filter chain in place of the inversion (vf_jpeg_chain*); tickets are invert tickets ----
     def jpeg_chain(self, jpegs: Sequence, steps: Sequence, quality: int, subsamp: int, flags: int = 0) -> list:

@@ -576,10 +576,217 @@ def transform_frames(frames: Sequence, mix, outs: Optional[List] = None, ctx: Op
                         lambda *a: (ctx or get_context()).mix_frames_host(*a, *mix.args))
 
 
+# -- separable filter: cv2.sepFilter2D, cv2.blur, cv2.boxFilter -----------------------------------------
+
+SEP_MAX_TAPS = 31  # per axis (csrc/vf_sep_plan.h kMaxSide)
+
+
+def as_taps(k) -> tuple:
+    """The taps of one axis of a separable kernel in the library's form: ``(int16 taps, shift)``, meaning
+    ``taps / 2**shift``, with the smallest such shift.
+
+    ``k`` is a 1-D integer array (shift 0), an ``(ints, shift)`` pair (``vfilter.kernels.binomial_taps`` and
+    ``gaussian_taps`` build those), or a 1-D floating-point array that is *dyadic*, by ``as_kernel``'s
+    rules.  The count is odd and at most 31, every tap fits int16, ``0 <= shift <= 16``.  Anything else
+    raises ``ValueError`` with the reason."""
+    shift = 0
+    if isinstance(k, tuple) and len(k) == 2 and np.ndim(k[1]) == 0 and np.ndim(k[0]) == 1:
+        k, shift = k
+        if int(shift) != shift:
+            raise ValueError(f"sep_filter2d: shift must be an integer, not {shift!r}")
+        shift = int(shift)
+        t = np.asarray(k)
+        if t.dtype.kind not in "iub":
+            if t.dtype.kind != "f" or not np.array_equal(t, np.rint(t)):
+                raise ValueError("sep_filter2d: the taps of a (taps, shift) pair must be integers")
+    else:
+        t = np.asarray(k)
+    if t.ndim != 1 or t.size == 0:
+        raise ValueError(f"sep_filter2d: the taps of an axis are a 1-D array, not shape {t.shape}")
+    if t.size % 2 == 0 or t.size > SEP_MAX_TAPS:
+        raise ValueError(f"sep_filter2d: {t.size} taps; the count must be odd and at most {SEP_MAX_TAPS}")
+    if not 0 <= shift <= 16:
+        raise ValueError(f"sep_filter2d: shift = {shift} outside 0..16")
+    if t.dtype.kind == "f" and not np.isfinite(t).all():
+        raise ValueError("sep_filter2d: the taps have a non-finite entry")
+    if t.dtype.kind == "f" and not np.array_equal(t, np.rint(t)):
+        t = t.astype(np.float64)
+        for s in range(1, 17):
+            scaled = t * float(1 << s)  # exact: a power of two
+            if np.array_equal(scaled, np.rint(scaled)):
+                t, shift = scaled, s
+                break
+        else:
+            raise ValueError("sep_filter2d: the taps are not dyadic (no s in 0..16 makes taps * 2**s integral); "
+                             "give integer taps and a shift, or a divisor")
+    elif t.dtype.kind not in "iubf":
+        raise ValueError(f"sep_filter2d: taps of dtype {t.dtype}")
+    w = np.asarray(np.rint(t) if t.dtype.kind == "f" else t).astype(np.int64)
+    while shift > 0 and not (w & 1).any():  # the smallest shift
+        w >>= 1
+        shift -= 1
+    if int(w.max()) > 32767 or int(w.min()) < -32768:
+        raise ValueError("sep_filter2d: a tap does not fit 16 bits")
+    return np.ascontiguousarray(w, dtype=np.int16), shift
+
+
+def _sep_sides(name: str, ksize) -> tuple:
+    """``ksize`` -- an int, or ``(width, height)`` in cv2's order -- as odd ``(kw, kh)`` of at most 31."""
+    try:
+        kw, kh = (ksize, ksize) if np.ndim(ksize) == 0 else ksize
+        if int(kw) != kw or int(kh) != kh:
+            raise TypeError
+        kw, kh = int(kw), int(kh)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: ksize is an int or (width, height), not {ksize!r}") from None
+    if kw < 1 or kh < 1 or kw > SEP_MAX_TAPS or kh > SEP_MAX_TAPS or kw % 2 == 0 or kh % 2 == 0:
+        raise ValueError(f"{name}: a {kw} x {kh} kernel; sides must be odd and at most {SEP_MAX_TAPS} "
+                         "(an even side has no centre)")
+    return kw, kh
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Separable:
+    """``cv2.sepFilter2D`` with the horizontal taps ``kx`` and the vertical taps ``ky`` (each as for
+    ``as_taps``; ``ky=None``: ``kx``), copied: ``dst = clamp(round(sum_j ky[j] sum_i kx[i] src / scale))``, exact in
+    integers, with one rounding at the end.  The scale is ``2**shift`` -- the shifts of the two axes
+    and ``shift`` add up, to at most 16, and the smallest common shift is taken -- rounded
+    ``rounding`` ("half_even", cv2's float path; "half_up", ``(x + half) >> shift``, cv2's 8-bit fixed-point
+    path), or the odd ``divisor`` (at most 1023, to nearest: no tie exists), not both.
+    ``sum|kx| * sum|ky| <= 65536``.  ``Separable.box`` is ``cv2.blur`` / ``cv2.boxFilter``, ``Separable.gaussian``
+    a fixed-point Gaussian."""
+    kx: np.ndarray  # int16, read-only
+    ky: np.ndarray
+    shift: int
+    divisor: int
+    rounding: str
+    rounding_code: int
+    border: str
+    border_code: int
+    family = "sep"
+
+    def __init__(self, kx, ky=None, shift=None, divisor=None, rounding: str = "half_even",
+                 border: str = "reflect101"):
+        if isinstance(kx, Separable) or isinstance(ky, Separable):
+            raise ValueError("Separable: kx and ky are taps, not a Separable")
+        code = rounding_code(rounding)
+        bcode = border_code(border)
+        tx, sx = as_taps(kx)
+        ty, sy = (tx.copy(), sx) if ky is None else as_taps(ky)
+        extra = 0
+        if shift is not None:
+            if isinstance(shift, bool) or int(shift) != shift or shift < 0:
+                raise ValueError(f"Separable: shift = {shift!r} is not a non-negative integer")
+            extra = int(shift)
+        total = sx + sy + extra
+        x, y = tx.astype(np.int64), ty.astype(np.int64)
+        while total > 0 and (not (x & 1).any() or not (y & 1).any()):  # the smallest common shift
+            if not (x & 1).any():
+                x >>= 1
+            else:
+                y >>= 1
+            total -= 1
+        if total > 16:
+            raise ValueError(f"Separable: the shifts add up to {total}; at most 16")
+        d = 1 if divisor is None else divisor
+        if isinstance(d, bool) or int(d) != d or d < 1 or d > 1023 or d % 2 == 0:
+            raise ValueError(f"Separable: divisor = {divisor!r}; a divisor is odd and 1..1023")
+        d = int(d)
+        if d != 1 and total != 0:
+            raise ValueError(f"Separable: a shift of {total} together with divisor = {d}; a filter scales by one of them")
+        prod = int(np.abs(x).sum()) * int(np.abs(y).sum())
+        if prod > 65536:
+            raise ValueError(f"Separable: sum|kx| * sum|ky| = {prod} exceeds 65536")
+        tx, ty = x.astype(np.int16), y.astype(np.int16)
+        tx.flags.writeable = False
+        ty.flags.writeable = False
+        fields = {"kx": tx, "ky": ty, "shift": total, "divisor": d, "rounding": rounding, "rounding_code": code,
+                  "border": border, "border_code": bcode}
+        for name, v in fields.items():
+            object.__setattr__(self, name, v)
+
+    @classmethod
+    def box(cls, ksize, normalize: bool = True, border: str = "reflect101") -> "Separable":
+        """``cv2.blur(src, ksize)`` / ``cv2.boxFilter(src, -1, ksize, normalize=...)``: all taps 1 and the divisor
+        ``width * height`` (``normalize=False``: the saturating sum).  ``ksize`` is an int or ``(width, height)``;
+        sides are odd, so the area is."""
+        kw, kh = _sep_sides("box", ksize)
+        return cls(np.ones(kw, np.int16), np.ones(kh, np.int16), divisor=kw * kh if normalize else None,
+                   border=border)
+
+    @classmethod
+    def gaussian(cls, ksize, sigma, bits: int = 8, rounding: str = "half_up",
+                 border: str = "reflect101") -> "Separable":
+        """A Gaussian in fixed point: ``vfilter.kernels.gaussian_taps(side, sigma, bits)`` on each axis and one
+        ``(x + half) >> 2 * bits`` at the end (the structure of cv2's 8-bit path; the taps are this project's
+        quantisation, not cv2's).  ``ksize`` an int or ``(width, height)``, ``sigma`` a number or ``(sigma_x,
+        sigma_y)``; ``bits <= 8``."""
+        from .kernels import gaussian_taps
+        kw, kh = _sep_sides("gaussian", ksize)
+        sx, sy = (sigma, sigma) if np.ndim(sigma) == 0 else sigma
+        if int(bits) != bits or not 1 <= bits <= 8:
+            raise ValueError(f"gaussian: bits = {bits!r}; two axes of `bits` bits stay within 16, so 1..8")
+        return cls(gaussian_taps(kw, sx, bits), gaussian_taps(kh, sy, bits), rounding=rounding, border=border)
+
+    @property
+    def args(self) -> tuple:
+        return self.kx, self.ky, self.shift, self.divisor, self.rounding_code, self.border_code
+
+
+def _sep_one(name: str, src, sep: Separable, dst, ctx) -> np.ndarray:
+    src = np.ascontiguousarray(_conv_frame(name, src))
+    if dst is src:
+        raise ValueError(f"{name}: dst may not be src (the filter reads neighbours)")
+    dst = _rank_dst(name, src, dst)
+    channels = 1 if src.ndim == 2 else src.shape[2]
+    if src.size:
+        (ctx or get_context()).sep_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, *sep.args)
+    return dst
+
+
+def sep_filter2d(src: np.ndarray, kx, ky=None, shift=None, divisor=None, rounding: str = "half_even",
+                 border: str = "reflect101", dst: Optional[np.ndarray] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.sepFilter2D(src, -1, kx, ky)`` on uint8 ``H x W`` or ``H x W x 3`` input (correlation,
+    anchor at the centre, reflect-101 by default), exact for what ``Separable`` accepts; ``kx`` may be a
+    ``Separable`` (then the other filter arguments stay at their defaults).  It equals ``filter2d`` with
+    ``outer(ky, kx)`` wherever both exist, with up to 31 taps an axis.  ``dst`` as for ``filter2d``: not ``src``."""
+    if isinstance(kx, Separable):
+        if ky is not None or shift is not None or divisor is not None:
+            raise ValueError("sep_filter2d: a Separable carries its own taps and scale")
+        sep = kx
+    else:
+        sep = Separable(kx, ky, shift, divisor, rounding, border)
+    return _sep_one("sep_filter2d", src, sep, dst, ctx)
+
+
+def blur(src: np.ndarray, ksize, border: str = "reflect101", dst: Optional[np.ndarray] = None,
+         ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.blur(src, ksize)``: the mean over ``ksize`` (an int, or ``(width, height)``; odd sides up
+    to 31), rounded to nearest."""
+    return _sep_one("blur", src, Separable.box(ksize, True, border), dst, ctx)
+
+
+def box_filter(src: np.ndarray, ksize, normalize: bool = True, border: str = "reflect101",
+               dst: Optional[np.ndarray] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.boxFilter(src, -1, ksize, normalize=normalize)``; ``normalize=False`` is the saturating
+    sum."""
+    return _sep_one("box_filter", src, Separable.box(ksize, normalize, border), dst, ctx)
+
+
+def sep_frames(frames: Sequence, sep: Separable, outs: Optional[List] = None, ctx: Optional[Context] = None) -> List:
+    """A ``Separable`` over separately stored frames of one channel count and mixed sizes in one call.
+    Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
+    if not isinstance(sep, Separable):
+        raise ValueError("sep_frames: sep is a Separable")
+    return _frames_call("sep_frames", [_conv_frame("sep_frames", f) for f in frames], outs,
+                        lambda *a: (ctx or get_context()).sep_frames_host(*a, *sep.args))
+
+
 # -- filter chains: a program of filters between one upload and one download ----------------------
 
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
 STEP_MIX = 5  # VF_STEP_MIX: 4 names no kind and stays refused
+STEP_SEP = 7  # VF_STEP_SEP: 6 stays refused as well
 BINARY_OPS = {"subtract": 0, "add": 1, "absdiff": 2, "min": 3, "max": 4}  # VF_BIN_*
 CHAIN_MAX_STEPS = 8  # VF_CHAIN_MAX_STEPS
 MORPH_OPS = ("erode", "dilate", "open", "close", "gradient", "tophat", "blackhat")
@@ -592,7 +799,7 @@ class Combine:
     """A two-input step of a ``Chain``: ``op(a, b)`` per byte, ``op`` one of "subtract"
     (``max(a - b, 0)``), "add" (``min(a + b, 255)``), "absdiff", "min", "max" -- ``cv2.subtract``,
     ``cv2.add``, ``cv2.absdiff``, ``cv2.min``, ``cv2.max`` on uint8.  ``a`` and ``b`` are each a filter
-    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, another ``Combine``), a ``Chain``, or ``None``
+    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``, another ``Combine``), a ``Chain``, or ``None``
     for the value entering the ``Combine``; both are applied to that value."""
     op: str
     op_code: int
@@ -603,7 +810,7 @@ class Combine:
         if op not in BINARY_OPS:
             raise ValueError(f"combine: op must be one of {sorted(BINARY_OPS)}, not {op!r}")
         for name, v in (("a", a), ("b", b)):
-            if v is not None and not isinstance(v, _CHAIN_ITEMS + (Chain,)):
+            if v is not None and not isinstance(v, _CHAIN_ITEMS + (Chain, Combine)):  # another Combine nests
                 raise ValueError(f"combine: {name} is a filter value, a Chain or None, not {type(v).__name__}")
         for name, v in (("op", op), ("op_code", BINARY_OPS[op]), ("a", a), ("b", b)):
             object.__setattr__(self, name, v)
@@ -621,7 +828,10 @@ def _unary_step(f, a: int) -> tuple:
         return (STEP_RANK, a, 0, f.op_code, f.element, 0, f.border_code)
     if isinstance(f, Mix):
         return (STEP_MIX, a, 0, f.rounding_code, f.matrix, f.shift, 0)
-    raise ValueError(f"chain: a step is Invert, Table, Kernel, Rank, Mix, Combine or Chain, not {type(f).__name__}")
+    if isinstance(f, Separable):
+        return (STEP_SEP, a, 0, f.rounding_code, (f.kx, f.ky, f.divisor), f.shift, f.border_code)
+    raise ValueError("chain: a step is Invert, Table, Kernel, Rank, Mix, Separable, Combine or Chain, "
+                     f"not {type(f).__name__}")
 
 
 def _check_program(steps: Sequence[tuple]) -> None:
@@ -706,7 +916,7 @@ class Chain:
         return len(self.steps)
 
 
-_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix)
+_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable)
 
 
 def _lower(item, cur: int, prog: List[tuple]) -> int:

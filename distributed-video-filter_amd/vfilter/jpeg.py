@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import Invert, Kernel, Morph, Rank, Table, _as_chain, _as_mix
+from .filters import Invert, Kernel, Morph, Rank, Separable, Table, _as_chain, _as_mix
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -94,7 +94,7 @@ class TurboJPEG:
         return self.ctx.jpeg_encode(list(imgs), pixel_format, quality, jpeg_subsample,
                                     self._enc_flags(flags, quality))
 
-    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank) between decode and encode.  The
+    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank, Mix, Separable, Chain) between decode and encode.  The
     # ``invert*``, ``lut*`` and ``filter2d*`` methods below are these three with their filter built
     # from the call's own arguments.
     def filter_batch(self, jpeg_bufs: Sequence, filt, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
@@ -218,6 +218,40 @@ class TurboJPEG:
     def transform_batch(self, jpeg_bufs: Sequence, m, rounding: str = "half_even", quality: int = 85,
                         jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
         return self.filter_batch(jpeg_bufs, _as_mix("transform_batch", m, rounding), quality, jpeg_subsample, flags)
+
+    # -- a separable filter: cv2.sepFilter2D / cv2.blur between decode and encode --------------------------
+    # The submit forms go through ``filter_batch_submit*`` with a ``vfilter.filters.Separable``.
+    @staticmethod
+    def _as_sep(kx, ky, shift, divisor, rounding, border) -> Separable:
+        if not isinstance(kx, Separable):
+            return Separable(kx, ky, shift, divisor, rounding, border)
+        if ky is not None or shift is not None or divisor is not None:
+            raise ValueError("sep_filter2d: a Separable carries its own taps and scale")
+        return kx
+
+    def sep_filter2d(self, jpeg_buf, kx, ky=None, shift=None, divisor=None, rounding: str = "half_even",
+                     border: str = "reflect101", quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                     flags: int = 0) -> bytes:
+        """``encode(cv2.sepFilter2D(decode(jpeg_buf), -1, kx, ky))`` on the GPU, the pixels never leaving it.
+        The filter arguments as for ``vfilter.sep_filter2d`` (``kx`` may be a ``Separable``); the taps are
+        applied to each channel of the decoded BGR frame."""
+        return self.filter_batch([jpeg_buf], self._as_sep(kx, ky, shift, divisor, rounding, border), quality,
+                                 jpeg_subsample, flags)[0]
+
+    def sep_filter2d_batch(self, jpeg_bufs: Sequence, kx, ky=None, shift=None, divisor=None,
+                           rounding: str = "half_even", border: str = "reflect101", quality: int = 85,
+                           jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, self._as_sep(kx, ky, shift, divisor, rounding, border), quality,
+                                 jpeg_subsample, flags)
+
+    def blur(self, jpeg_buf, ksize, border: str = "reflect101", quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+             flags: int = 0) -> bytes:
+        """``encode(cv2.blur(decode(jpeg_buf), ksize))`` on the GPU; ``ksize`` as for ``vfilter.blur``."""
+        return self.filter_batch([jpeg_buf], Separable.box(ksize, True, border), quality, jpeg_subsample, flags)[0]
+
+    def blur_batch(self, jpeg_bufs: Sequence, ksize, border: str = "reflect101", quality: int = 85,
+                   jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, Separable.box(ksize, True, border), quality, jpeg_subsample, flags)
 
     # -- a filter chain (vfilter.filters.Chain) between one decode and one encode ------------------------
     def chain(self, jpeg_buf, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:

@@ -99,3 +99,56 @@ def unsharp(amount=1):
     if shift > 16 or np.abs(w).sum() > 65536:
         raise ValueError(f"unsharp: amount = {amount!r} needs more precision than a kernel holds")
     return w.astype(np.int16), shift
+
+
+# -- taps for vfilter.sep_filter2d / vfilter.Separable: 1-D, one axis ----------------------------------
+# Each builder returns ``(taps, shift)``: a 1-D int16 array and the power of two ONE axis divides
+# by.  The shifts of the two axes add and their sum is at most 16.
+
+def binomial_taps(n: int):
+    """The binomial row of n taps, ``[1 2 1] / 4``, ``[1 4 6 4 1] / 16``, ...: ``(taps, n - 1)``.  Odd n up to
+    9, so that two axes of n - 1 bits each stay within 16 bits.  ``binomial_taps(7)`` on both axes is
+    ``gaussian7()`` in 14 taps."""
+    n = int(n)
+    if n < 1 or n > 9 or n % 2 == 0:
+        raise ValueError(f"binomial_taps: n = {n}; n is odd and at most 9")
+    row = np.array([1])
+    for _ in range(n - 1):
+        row = np.convolve(row, [1, 1])
+    return row.astype(np.int16), n - 1
+
+
+def gaussian_taps(ksize: int, sigma: float, bits: int = 8):
+    """A sampled Gaussian of ``ksize`` taps (odd, at most 31) and standard deviation ``sigma`` in fixed
+    point: ``(taps, bits)``, symmetric taps that sum to exactly ``2**bits``.
+
+    The quantisation is this project's, not cv2's: the samples ``exp(-x*x / (2 sigma^2))`` are scaled to
+    sum to ``2**bits`` and floored, and the units still missing go to the taps with the largest
+    remainders, a symmetric pair at a time from the centre outwards on equal remainders (an odd unit
+    goes to the centre tap).  ``cv2.GaussianBlur``'s own 8-bit taps may differ in the last unit."""
+    ksize, bits = int(ksize), int(bits)
+    if ksize < 1 or ksize > 31 or ksize % 2 == 0:
+        raise ValueError(f"gaussian_taps: ksize = {ksize}; ksize is odd and at most 31")
+    if not 1 <= bits <= 14:  # a tap of 2**bits fits int16
+        raise ValueError(f"gaussian_taps: bits = {bits} outside 1..14")
+    sigma = float(sigma)
+    if not np.isfinite(sigma) or sigma <= 0:
+        raise ValueError(f"gaussian_taps: sigma = {sigma!r} is not a positive number")
+    r = ksize // 2
+    x = np.arange(r + 1, dtype=np.float64)  # the centre and one side: the other side mirrors it
+    g = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    g *= float(1 << bits) / (g[0] + 2.0 * g[1:].sum())
+    q = np.floor(g).astype(np.int64)
+    missing = (1 << bits) - int(q[0] + 2 * q[1:].sum())
+    rem = g - q
+    order = sorted(range(1, r + 1), key=lambda i: (-rem[i], i))  # side taps: a unit costs two
+    while missing >= 2 and order:
+        for i in order:
+            if missing < 2:
+                break
+            q[i] += 1
+            missing -= 2
+    q[0] += missing  # an odd unit, or all of them when ksize == 1
+    taps = np.concatenate([q[:0:-1], q])
+    assert int(taps.sum()) == 1 << bits
+    return taps.astype(np.int16), bits

@@ -474,6 +474,57 @@ int vf_jpeg_bench_mix(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jp
                       const int32_t *matrix, int shift, int rounding, int quality, int subsamp,
                       int flags, int iters, float *ms, float *stage_ms);
 
+/* ---- separable filter (cv2.sepFilter2D, cv2.blur, cv2.boxFilter, wide Gaussians) -------------
+ * For uint8 frames of 1 or 3 interleaved channels, exact in integers.  `kx` holds
+ * `kw` horizontal taps and `ky` `kh` vertical taps, int16, HOST pointers read during the call
+ * only; kw and kh are odd and at most 31, the anchor is the centre, the operation correlation:
+ *   acc = sum_j ky[j] * sum_i kx[i] * src[by(y + j - kh/2)][bx(x + i - kw/2)]   exact, 32-bit
+ *   q   = acc                                  shift == 0 and divisor == 1
+ *       = acc / 2^shift rounded                0 < shift <= 16: VF_ROUND_HALF_EVEN or VF_ROUND_HALF_UP
+ *       = floor((2 acc + d) / (2 d))           divisor d, odd, 1 < d <= 1023: to nearest (no tie exists)
+ *   dst = min(max(q, 0), 255)
+ * which is vf_conv_* with the kernel outer(ky, kx) wherever both exist.  sum|kx| * sum|ky| <=
+ * 65536; `divisor` is 1 for none, and a shift and a divisor exclude each other; `border` is a
+ * VF_BORDER_*.  cv2.blur(src, (w, h)): all taps 1, divisor w * h.  Anything else, NULL taps, an
+ * unknown rounding or border is VF_E_INVALID with the reason, before any GPU work. */
+
+/* The output tile of one workgroup of the separable kernel for kw x kh taps: *row_bytes bytes
+ * of *rows rows.  Makes no HIP call.  VF_E_INVALID for tap counts the filter refuses. */
+int vf_sep_tile(int kw, int kh, int *row_bytes, int *rows);
+
+/* Enqueue the filter on `stream` over one device-resident frame, as vf_conv_device: out of place
+ * (src and dst must not overlap), any alignment, returns after the launch. */
+int vf_sep_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                  const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor,
+                  int rounding, int border, void *stream);
+
+/* The filter on `n` separately allocated host frames, synchronous, as vf_conv_frames_host:
+ * srcs[i] == dsts[i] is allowed; a frame larger than the context's staging is cut into bands of
+ * rows with halos of kh / 2 rows. */
+int vf_sep_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                       const int *widths, const int *heights, int n, int channels,
+                       const int16_t *kx, int kw, const int16_t *ky, int kh, int shift,
+                       int divisor, int rounding, int border);
+
+/* vf_jpeg_invert with the filter in place of the inversion: decode -> filter -> encode on the
+ * GPU, on the decoded BGR frame. */
+int vf_jpeg_sep(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor,
+                int rounding, int border, int quality, int subsamp, int flags,
+                uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the filter (the taps are copied).  The ticket is an invert ticket. */
+int vf_jpeg_sep_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                       const int16_t *kx, int kw, const int16_t *ky, int kh, int shift,
+                       int divisor, int rounding, int border, int quality, int subsamp, int flags,
+                       uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the filter between the decode and the encode. */
+int vf_jpeg_bench_sep(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                      const int16_t *kx, int kw, const int16_t *ky, int kh, int shift, int divisor,
+                      int rounding, int border, int quality, int subsamp, int flags, int iters,
+                      float *ms, float *stage_ms);
+
 /* ---- filter chains (cv2.morphologyEx, difference of blurs, ...) -----------------------------
  * A program is a straight-line list of 1 .. VF_CHAIN_MAX_STEPS steps over values.
  * Value 0 is the input frame (uint8, 1 or 3 interleaved channels, packed rows), value i the result
@@ -489,17 +540,20 @@ int vf_jpeg_bench_mix(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jp
  *                   (cv2.subtract, cv2.add, cv2.absdiff, cv2.min, cv2.max on uint8)
  *   VF_STEP_MIX     cv2.transform: `data` is the 12 int32 [M | t] of vf_mix_*, with `shift`, and
  *                   `op` a VF_ROUND_*; 3-channel frames only
+ *   VF_STEP_SEP     the separable filter: `data` is 1 + kw + kh int32, the divisor (0 or 1: none),
+ *                   then kx, then ky; `kw`, `kh` the tap counts, `shift`, `op` a VF_ROUND_*, `border`
  * `data` is a HOST pointer, read during the call only.  VF_E_INVALID, before any GPU work: a step
  * that reads a later value or itself, a value other than the last that no step reads, a 3-channel
  * table or a colour matrix on 1-channel frames, more than VF_CHAIN_MAX_STEPS steps, and anything
  * the single-filter entry points refuse for a table, a kernel, an element or a matrix.
  * The VF_STEP_* values are not dense: 4 names no kind and stays refused ("unknown kind 4"), as
- * callers' checks of the refusal expect, so VF_STEP_MIX is 5. */
+ * callers' checks of the refusal expect, so VF_STEP_MIX is 5; 6 likewise, so VF_STEP_SEP is 7. */
 #define VF_STEP_TABLE  0
 #define VF_STEP_CONV   1
 #define VF_STEP_RANK   2
 #define VF_STEP_BINARY 3
 #define VF_STEP_MIX    5
+#define VF_STEP_SEP    7
 #define VF_BIN_SUBTRACT 0
 #define VF_BIN_ADD      1
 #define VF_BIN_ABSDIFF  2
@@ -510,11 +564,12 @@ int vf_jpeg_bench_mix(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jp
 typedef struct vf_step {
   int kind;         /* a VF_STEP_* */
   int a, b;         /* operand values; b for VF_STEP_BINARY only */
-  int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_*; VF_STEP_MIX: a VF_ROUND_* */
-  const void *data; /* the table, the int16 weights, the element or the 12 int32 (host memory) */
-  int kw, kh;       /* VF_STEP_CONV, VF_STEP_RANK */
-  int shift;        /* VF_STEP_CONV, VF_STEP_MIX */
-  int border;       /* VF_STEP_CONV, VF_STEP_RANK: a VF_BORDER_* */
+  int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_*; VF_STEP_MIX, VF_STEP_SEP: a VF_ROUND_* */
+  const void *data; /* the table, the int16 weights, the element or the int32 of a matrix or of
+                       separable taps (host memory) */
+  int kw, kh;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP */
+  int shift;        /* VF_STEP_CONV, VF_STEP_MIX, VF_STEP_SEP */
+  int border;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP: a VF_BORDER_* */
   int channels;     /* VF_STEP_TABLE: 1 or 3 */
 } vf_step;
 
