@@ -33,6 +33,7 @@
 #include "vf_host_mem.h"
 #include "vf_internal.h"
 #include "vf_sep_plan.h"
+#include "vf_level_plan.h"
 #include "vf_jpeg_codec.h"
 #include "vf_lut_split.h"
 #include "vf_conv_bands.h"
@@ -90,6 +91,12 @@ struct vf_ctx {
   // program_frames_host's intermediate values: device buffers sized like raw_din, allocated by the
   // first program that needs them (raw_mu held; one of a single step needs none), freed with the context
   std::vector<uint8_t *> raw_scratch;
+  // the level filter's histogram words (vf_level.hip): level_hist for program_frames_host and
+  // vf_hist_frames_host (raw_mu held, raw_stream), level::kHistWords for each step of a program;
+  // level_dev_hist for vf_level_device (level_mu guards its creation; the caller's stream orders its use)
+  uint32_t *level_hist = nullptr;
+  std::mutex level_mu;
+  uint32_t *level_dev_hist = nullptr;
 };
 
 namespace {
@@ -270,6 +277,8 @@ VF_EXPORT int vf_destroy(vf_ctx *ctx) {
     (void)hipFree(ctx->raw_din);
     (void)hipFree(ctx->raw_dout);
     for (uint8_t *p : ctx->raw_scratch) (void)hipFree(p);
+    if (ctx->level_hist) (void)hipFree(ctx->level_hist);
+    if (ctx->level_dev_hist) (void)hipFree(ctx->level_dev_hist);
     (void)hipStreamDestroy(ctx->raw_stream);
   }
   for (vf::jpeg::Codec *c : ctx->jpeg_all) delete c;  // each synchronises its stream first
@@ -542,7 +551,7 @@ namespace vf {
 
 hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const std::vector<chain::Launch> &launches,
                         uint8_t *const *bufs, uint8_t *out, int w, int channels, int frame_h, int conv_form,
-                        const LaunchCfg &cfg, hipStream_t stream) {
+                        uint32_t *hist, const LaunchCfg &cfg, hipStream_t stream) {
   const size_t row = (size_t)w * (size_t)channels;
   for (const chain::Launch &l : launches) {
     const chain::Step &s = prog.steps[(size_t)l.step - 1];
@@ -565,6 +574,10 @@ hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const
     else if (s.kind == chain::kSep)
       e = launch_sep(a, dst, w, channels, frame_h, l.y0, l.nrows, l.src0, l.nsrc, s.taps_x.data(), s.kw, s.taps_y.data(),
                      s.kh, s.shift, s.divisor, s.op, s.border, sep_form_env(), stream);
+    else if (s.kind == chain::kLevel)  // whole frames only (chain::whole_frame): nbytes is all of the operand
+      e = hist ? launch_level(a, dst, nbytes, channels, s.op, s.mask, s.link, s.clip_lo, s.clip_hi,
+                              hist + (size_t)(l.step - 1) * level::kHistWords, cfg, stream)
+               : hipErrorInvalidValue;
     else
       e = hipErrorInvalidValue;  // no kernel for the kind: validate() lets none through
     if (e != hipSuccess) return e;
@@ -593,6 +606,7 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
   int rc = chain_program(ctx, fn, steps, nsteps, channels, &prog, &masks);
   if (rc != VF_OK) return rc;
   const int ry = vf::chain::reach(prog);
+  const bool whole = vf::chain::whole_frame(prog);  // a level step: every frame is one band, or refused
   if (n < 0) return set_err(ctx, VF_E_INVALID, 0, "%s: n < 0", fn);
   if (n > 0 && (!srcs || !dsts || !widths || !heights)) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL array", fn);
   // one upload + launch + download per band (vf_conv_bands.h); most frames are one band
@@ -612,7 +626,19 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
     if (overlaps_partially(srcs[i], dsts[i], row * (size_t)heights[i]))
       return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d src/dst partially overlap", fn, i);
     std::vector<vf::conv::Band> bs;
-    if (!vf::conv::bands(widths[i], heights[i], channels, ry, cap, &bs))
+    if (whole) {
+      std::string why;
+      for (const vf::chain::Step &s : prog.steps)
+        if (s.kind == vf::chain::kLevel &&
+            !vf::level::pixels_ok((uint64_t)widths[i] * (uint64_t)heights[i], s.mask, s.link, channels, &why))
+          return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
+      if (row * (size_t)heights[i] > cap)
+        return set_err(ctx, VF_E_INVALID, 0,
+                       "%s: frame %d: %d rows of %zu bytes do not fit the context's %zu-byte staging (a level step "
+                       "reads the whole frame: it is not cut into bands)",
+                       fn, i, heights[i], row, cap);
+      bs.push_back(vf::conv::Band{0, heights[i], 0, heights[i]});
+    } else if (!vf::conv::bands(widths[i], heights[i], channels, ry, cap, &bs))
       return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %d rows of %zu bytes do not fit the context's %zu-byte staging",
                      fn, i, 2 * ry + 1, row, cap);
     for (const vf::conv::Band &b : bs) {
@@ -634,6 +660,11 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
     void *p = nullptr;
     VF_HIP(ctx, hipMalloc(&p, alloc));
     ctx->raw_scratch.push_back(static_cast<uint8_t *>(p));
+  }
+  if (whole && !ctx->level_hist) {
+    void *p = nullptr;
+    VF_HIP(ctx, hipMalloc(&p, (size_t)vf::chain::kMaxSteps * vf::level::kHistWords * sizeof(uint32_t)));
+    ctx->level_hist = static_cast<uint32_t *>(p);
   }
   uint8_t *base[vf::chain::kMaxSteps + 1] = {};  // base[0]: each piece's upload; a value per step at the most
   std::copy(ctx->raw_scratch.begin(), ctx->raw_scratch.end(), base + 1);
@@ -659,7 +690,7 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
       base[0] = din;
       const int w = widths[p.frame], h = heights[p.frame];
       VF_HIP(ctx, vf::run_launches(prog, masks.data(), vf::chain::band_launches(prog, bufs, h, p.b.y0, p.b.y1, p.b.s0, true),
-                                   base, dout, w, channels, h, form, ctx->cfg, st));
+                                   base, dout, w, channels, h, form, whole ? ctx->level_hist : nullptr, ctx->cfg, st));
       at[j] = cout;
       cin += (in_bytes + 15) & ~(size_t)15;
       cout += (out_bytes + 15) & ~(size_t)15;
@@ -866,7 +897,141 @@ VF_EXPORT int vf_sep_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_
   return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
 }
 
-// ---- filter chains: a program of table / conv / rank / binary / mix / sep steps on raw frames -------
+// ---- level filter (cv2.equalizeHist, auto-levels) and the histogram on raw frames ---------------------
+
+namespace {
+
+// The filter arguments every vf_level_* / vf_jpeg_level* entry point and a VF_STEP_LEVEL step share
+// (vf_level_plan.h has the limits).
+int check_level(vf_ctx *ctx, const char *fn, int rule, int mask, int link, int clip_lo, int clip_hi, int channels) {
+  std::string why;
+  if (!vf::level::limits_ok(rule, mask, link, clip_lo, clip_hi, channels, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  return VF_OK;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_hist_device(vf_ctx *ctx, const void *dsrc, size_t nbytes, int channels, uint32_t *dhist, void *stream) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_hist_device";
+  const int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if (nbytes % (size_t)channels != 0)
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %zu bytes are not whole %d-channel pixels", fn, nbytes, channels);
+  std::string why;
+  if (!vf::level::pixels_ok(nbytes / (size_t)channels, 0, 0, channels, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  if (!dhist) return set_err(ctx, VF_E_INVALID, 0, "%s: hist is NULL", fn);
+  if ((uintptr_t)dhist & 3) return set_err(ctx, VF_E_INVALID, 0, "%s: hist is not 4-byte aligned", fn);
+  if (nbytes != 0 && !dsrc) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL buffer", fn);
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, hipMemsetAsync(dhist, 0, (size_t)channels * 256 * sizeof(uint32_t), (hipStream_t)stream));
+  VF_HIP(ctx, vf::launch_hist(dsrc, nbytes, channels, dhist, ctx->cfg, (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_hist_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, const size_t *nbytes, int n, int channels,
+                                  uint32_t *hists) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_hist_frames_host";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if (n < 0) return set_err(ctx, VF_E_INVALID, 0, "%s: n < 0", fn);
+  if (n > 0 && (!srcs || !nbytes || !hists)) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL array", fn);
+  for (int i = 0; i < n; ++i) {
+    if (nbytes[i] % (size_t)channels != 0)
+      return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %zu bytes are not whole %d-channel pixels", fn, i, nbytes[i],
+                     channels);
+    std::string why;
+    if (!vf::level::pixels_ok(nbytes[i] / (size_t)channels, 0, 0, channels, &why))
+      return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
+    if (nbytes[i] != 0 && !srcs[i]) return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d has a NULL buffer", fn, i);
+  }
+  if (n == 0) return VF_OK;
+  const size_t words = (size_t)channels * 256;
+  std::lock_guard<std::mutex> lk(ctx->raw_mu);
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t cap = ctx->raw_cap, alloc = ((cap + 15 + 15) & ~(size_t)15);
+  if ((rc = raw_staging(ctx, fn, alloc)) != VF_OK) return rc;
+  // the frames' words sit in raw_dout, a group of as many frames as it holds at a time; a frame's
+  // bytes go through raw_din in pieces of whole pixels that keep the caller's offset mod 16, one
+  // fill of raw_din after the other, every piece added to the frame's words
+  const size_t group = alloc / (words * sizeof(uint32_t));
+  if (group == 0) return set_err(ctx, VF_E_INVALID, 0, "%s: the context's %zu-byte staging holds no histogram", fn, cap);
+  const size_t piece_max = cap / 48 * 48;  // whole pixels and whole 16-B vectors
+  if (piece_max == 0) return set_err(ctx, VF_E_INVALID, 0, "%s: the context's %zu-byte staging holds no pixel", fn, cap);
+  hipStream_t st = ctx->raw_stream;
+  uint32_t *dh = reinterpret_cast<uint32_t *>(ctx->raw_dout);
+  for (size_t g0 = 0; g0 < (size_t)n; g0 += group) {
+    const size_t g1 = std::min((size_t)n, g0 + group);
+    VF_HIP(ctx, hipMemsetAsync(dh, 0, (g1 - g0) * words * sizeof(uint32_t), st));
+    size_t cur = 0;
+    for (size_t i = g0; i < g1; ++i) {
+      for (size_t off = 0; off < nbytes[i];) {
+        const size_t len = std::min(piece_max, nbytes[i] - off);
+        const size_t room = (len + 15 + 15) & ~(size_t)15;
+        if (cur + room > alloc) {  // raw_din is full: let its pieces be counted before they are overwritten
+          VF_HIP(ctx, hipStreamSynchronize(st));
+          cur = 0;
+        }
+        uint8_t *din = ctx->raw_din + cur + ((uintptr_t)(srcs[i] + off) & 15);
+        VF_HIP(ctx, hipMemcpyAsync(din, srcs[i] + off, len, hipMemcpyHostToDevice, st));
+        VF_HIP(ctx, vf::launch_hist(din, len, channels, dh + (i - g0) * words, ctx->cfg, st));
+        cur += room;
+        off += len;
+      }
+    }
+    VF_HIP(ctx, hipMemcpyAsync(hists + g0 * words, dh, (g1 - g0) * words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VF_HIP(ctx, hipStreamSynchronize(st));
+  }
+  return VF_OK;
+}
+
+VF_EXPORT int vf_level_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels, int rule,
+                              int mask, int link, int clip_lo, int clip_hi, void *stream) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_level_device";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_level(ctx, fn, rule, mask, link, clip_lo, clip_hi, channels)) != VF_OK) return rc;
+  if (width == 0 && height == 0) return VF_OK;  // the empty frame
+  if ((rc = check_frame_shape(ctx, fn, width, height, channels)) != VF_OK) return rc;
+  std::string why;
+  if (!vf::level::pixels_ok((uint64_t)width * (uint64_t)height, mask, link, channels, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL buffer", fn);
+  const size_t nbytes = (size_t)width * (size_t)channels * (size_t)height;
+  if (overlaps_partially((const uint8_t *)dsrc, (const uint8_t *)ddst, nbytes))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: src and dst partially overlap", fn);
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  {
+    std::lock_guard<std::mutex> lk(ctx->level_mu);
+    if (!ctx->level_dev_hist) {
+      void *p = nullptr;
+      VF_HIP(ctx, hipMalloc(&p, vf::level::kHistWords * sizeof(uint32_t)));
+      ctx->level_dev_hist = static_cast<uint32_t *>(p);
+    }
+  }
+  VF_HIP(ctx, vf::launch_level(dsrc, ddst, nbytes, channels, rule, mask, link, clip_lo, clip_hi, ctx->level_dev_hist,
+                               ctx->cfg, (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_level_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                   const int *heights, int n, int channels, int rule, int mask, int link, int clip_lo,
+                                   int clip_hi) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_level_frames_host";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_level(ctx, fn, rule, mask, link, clip_lo, clip_hi, channels)) != VF_OK) return rc;
+  const int32_t data[4] = {mask, link, clip_lo, clip_hi};
+  const vf_step step{VF_STEP_LEVEL, 0, 0, rule, data, 0, 0, 0, 0, 0};  // a program of one step
+  return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
+}
+
+// ---- filter chains: a program of table / conv / rank / binary / mix / sep / level steps on raw frames
 
 namespace {
 
@@ -927,6 +1092,12 @@ int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps,
                           in.border)) != VF_OK)
         return rc;
       s.kw = in.kw, s.kh = in.kh, s.shift = in.shift, s.border = in.border;
+    } else if (in.kind == VF_STEP_LEVEL) {
+      // data: {mask, link, clip_lo, clip_hi} as int32; op: the rule
+      const int32_t *d = static_cast<const int32_t *>(in.data);
+      if (!d) return set_err(ctx, VF_E_INVALID, 0, "%s: the level step's data is NULL", at);
+      if ((rc = check_level(ctx, at, in.op, d[0], d[1], d[2], d[3], channels)) != VF_OK) return rc;
+      s.mask = d[0], s.link = d[1], s.clip_lo = d[2], s.clip_hi = d[3];
     } else if (in.kind != VF_STEP_BINARY) {
       return set_err(ctx, VF_E_INVALID, 0, "%s: unknown kind %d", at, in.kind);
     }
@@ -1402,6 +1573,15 @@ int sep_filter(vf_ctx *ctx, const char *fn, const int16_t *kx, int kw, const int
   return chain_filter(ctx, fn, &step, 1, out);
 }
 
+// The decoded frames are 3-channel BGR, grayscale inputs included.
+int level_filter(vf_ctx *ctx, const char *fn, int rule, int mask, int link, int clip_lo, int clip_hi, Filter *out) {
+  const int rc = check_level(ctx, fn, rule, mask, link, clip_lo, clip_hi, 3);
+  if (rc != VF_OK) return rc;
+  const int32_t data[4] = {mask, link, clip_lo, clip_hi};
+  const vf_step step{VF_STEP_LEVEL, 0, 0, rule, data, 0, 0, 0, 0, 0};
+  return chain_filter(ctx, fn, &step, 1, out);
+}
+
 }  // namespace
 
 VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
@@ -1616,6 +1796,36 @@ VF_EXPORT int vf_jpeg_bench_sep(vf_ctx *ctx, const uint8_t *const *jpegs, const 
   if (const int rc = sep_filter(ctx, "vf_jpeg_bench_sep", kx, kw, ky, kh, shift, divisor, rounding, border, &filter))
     return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_sep", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
+                           filter);
+}
+
+// ---- JPEG with the level filter in place of the inversion ---------------------------------------------
+
+VF_EXPORT int vf_jpeg_level(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int rule, int mask,
+                            int link, int clip_lo, int clip_hi, int quality, int subsamp, int flags, uint8_t *const *outs,
+                            const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = level_filter(ctx, "vf_jpeg_level", rule, mask, link, clip_lo, clip_hi, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_level", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
+}
+
+VF_EXPORT int vf_jpeg_level_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int rule,
+                                   int mask, int link, int clip_lo, int clip_hi, int quality, int subsamp, int flags,
+                                   uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = level_filter(ctx, "vf_jpeg_level_submit", rule, mask, link, clip_lo, clip_hi, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_level_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
+}
+
+VF_EXPORT int vf_jpeg_bench_level(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int rule,
+                                  int mask, int link, int clip_lo, int clip_hi, int quality, int subsamp, int flags,
+                                  int iters, float *ms, float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = level_filter(ctx, "vf_jpeg_bench_level", rule, mask, link, clip_lo, clip_hi, &filter)) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_level", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
                            filter);
 }
 

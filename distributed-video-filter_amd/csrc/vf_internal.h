@@ -92,17 +92,36 @@ hipError_t launch_sep(const void *dsrc, void *ddst, int width, int channels, int
 int sep_form_env();
 int sep_tile_rows(int kh);
 
-// The steps of a program as launches of the six kernels above (vf_api.hip): `launches` is
+// The level filter (vf_level.hip; cv2.equalizeHist, auto-levels) over nbytes of whole
+// pixels of 1 or 3 interleaved channels.  launch_hist ADDS the counts of the bytes to hist, channels x
+// 256 uint32 words in device memory (word c * 256 + v: the bytes of channel c equal to v), which the
+// caller zeroed; at most 2^32 - 1 pixels.  launch_level zeroes `hist` (16-B aligned, at least channels
+// x 256 words, the caller's scratch) on the stream, counts dsrc into it, and writes
+// table[channel][dsrc[i]] to ddst, the tables made from the histogram by vf_level_plan.h's
+// level_table: rule a VF_LEVEL_*, mask the levelled channels (0: all), link one table from the
+// masked channels' summed histograms, clips for the stretch rule.  Each pointer at any alignment;
+// ddst == dsrc exactly is allowed (the histogram is complete before the first byte is written), a
+// partial overlap is not (the caller checks).  Work queued on one stream may share one `hist`.
+// No device allocation; asynchronous on `stream`.
+hipError_t launch_hist(const void *dsrc, size_t nbytes, int channels, uint32_t *hist, const LaunchCfg &cfg,
+                       hipStream_t stream);
+hipError_t launch_level(const void *dsrc, void *ddst, size_t nbytes, int channels, int rule, int mask, int link,
+                        int clip_lo, int clip_hi, uint32_t *hist, const LaunchCfg &cfg, hipStream_t stream);
+
+// The steps of a program as launches of the seven kernels above (vf_api.hip): `launches` is
 // vf_chain_plan.h's band_launches of a band or whole frame, masks[i] step i + 1's element when it
 // is a rank step, bufs[k] the address of buffer k's origin row (the band's row s0), out the rows a
-// chain::kOut launch writes; conv_form as launch_conv's form.
+// chain::kOut launch writes; conv_form as launch_conv's form.  hist: the histogram words of the
+// program's level steps, level::kHistWords for each step of the program (step i's at (i - 1) *
+// kHistWords), device memory that the work queued on `stream` alone uses; NULL when
+// chain::whole_frame(prog) is false.
 namespace chain {
 struct Program;
 struct Launch;
 }  // namespace chain
 hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const std::vector<chain::Launch> &launches,
                         uint8_t *const *bufs, uint8_t *out, int w, int channels, int frame_h, int conv_form,
-                        const LaunchCfg &cfg, hipStream_t stream);
+                        uint32_t *hist, const LaunchCfg &cfg, hipStream_t stream);
 
 // Up to kMappedMax page-locked host ranges, by their device addresses, inverted in place over
 // PCIe by one launch (vf_kernels.hip invert_mapped_kernel; passed by value as kernel arguments).

@@ -892,6 +892,11 @@ int Codec::run_filter_encode(bool fastdct, std::string *err) {
     if (k != 0) CK(b.ensure(dpix_bytes_));  // d_pix_ holds the decoded frames: sized by prepare_decode
     base[(size_t)k] = b.as<uint8_t>();
   }
+  uint32_t *hist = nullptr;  // a level step's histogram words: the frames run in order on s_, so one set a step
+  if (chain::whole_frame(c.prog)) {
+    CK(d_level_hist_.ensure((size_t)chain::kMaxSteps * level::kHistWords * sizeof(uint32_t)));
+    hist = d_level_hist_.as<uint32_t>();
+  }
   const LaunchCfg cfg;
   std::vector<chain::Launch> launches;  // of a whole frame: they depend on its height alone
   int launches_h = -1;
@@ -901,7 +906,7 @@ int Codec::run_filter_encode(bool fastdct, std::string *err) {
     if (h != launches_h) launches = chain::band_launches(c.prog, c.bufs, h, 0, h, 0, false);
     launches_h = h;
     for (size_t k = 0; k < base.size(); ++k) at[k] = base[k] + F.out_off;
-    CK(run_launches(c.prog, c.masks.data(), launches, at.data(), nullptr, F.g.w, 3, h, 0, cfg, s_));
+    CK(run_launches(c.prog, c.masks.data(), launches, at.data(), nullptr, F.g.w, 3, h, 0, hist, cfg, s_));
   }
   return run_encode(1, fastdct, base[(size_t)c.bufs.result], err);
 }

@@ -16,6 +16,8 @@ distributor.py).
                ``sep_filter2d``, ``blur`` and ``box_filter`` (the ``cv2.sepFilter2D``, ``cv2.blur`` and
                ``cv2.boxFilter`` drop-ins: up to 31 taps an axis, the mean by an exact division),
                ``Separable`` and ``sep_frames``
+               ``equalize_hist`` (the ``cv2.equalizeHist`` drop-in), ``auto_levels``, ``calc_hist`` (the
+               histogram, counted on the GPU), ``Level``, ``level_frames`` and ``calc_hist_frames``
   colors       builders of the usual colour matrices (gray, swap_rb, sepia, saturation, gain, ...)
   kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
   elements     builders of the usual structuring elements (rect, cross)
@@ -33,6 +35,7 @@ from .filters import (Chain, Combine, Mix, Morph, Rank, as_element, as_kernel, a
                       invert_frames, lut, lut_frames, median_blur, morphology_ex, rank_frames, transform,
                       transform_frames)
 from .filters import Separable, as_taps, blur, box_filter, sep_filter2d, sep_frames  # noqa: F401
+from .filters import Level, auto_levels, calc_hist, calc_hist_frames, equalize_hist, level_frames  # noqa: F401
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
@@ -42,4 +45,5 @@ __all__ = [
     "Chain", "Combine", "Morph", "chain", "chain_frames", "morphology_ex",
     "Mix", "as_matrix", "transform", "transform_frames", "colors",
     "Separable", "as_taps", "sep_filter2d", "blur", "box_filter", "sep_frames",
+    "Level", "equalize_hist", "auto_levels", "calc_hist", "calc_hist_frames", "level_frames",
 ]

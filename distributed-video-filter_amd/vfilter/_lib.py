@@ -139,6 +139,20 @@ SIGNATURES = {
     "vf_jpeg_bench_sep": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
+    "vf_hist_device": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, _vp, _vp]),
+    "vf_hist_frames_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "vf_level_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "vf_level_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vf_jpeg_level": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_level_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_level": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, _c_float_p, _c_float_p]),
     "vf_binary_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
     "vf_chain_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
     "vf_jpeg_chain": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -152,6 +166,8 @@ SIGNATURES = {
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
 STEP_MIX = 5                                                # VF_STEP_MIX: 4 names no kind and stays refused
 STEP_SEP = 7                                                # VF_STEP_SEP: 6 stays refused as well
+STEP_LEVEL = 8                                              # VF_STEP_LEVEL: 9 stays refused as well
+LEVEL_EQUALIZE, LEVEL_STRETCH = 0, 1                        # VF_LEVEL_*
 CHAIN_MAX_STEPS = 8                                         # VF_CHAIN_MAX_STEPS
 ROUND_HALF_EVEN, ROUND_HALF_UP = 0, 1                       # VF_ROUND_*
 
@@ -576,6 +592,33 @@ class Context:
         self._check(self._lib.vf_sep_device(self._ctx, dsrc, ddst, width, height, channels, x.ctypes.data, x.size,
                                             y.ctypes.data, y.size, shift, divisor, rounding, border, stream or None))
 
+    # -- level filter (cv2.equalizeHist, auto-levels) and the histogram: vf_hist_*, vf_level_* ----------------
+    def hist_frames_host(self, srcs: Sequence, channels: int, hists: np.ndarray) -> None:
+        """The histograms of the frames ``srcs`` (``channels`` interleaved channels each, mixed sizes) into ``hists``,
+        a C-contiguous uint32 array of ``len(srcs) * channels * 256`` entries."""
+        n = len(srcs)
+        if hists.dtype != np.uint32 or not hists.flags.c_contiguous or hists.size != n * channels * 256:
+            raise ValueError("hists must be a C-contiguous uint32 array of len(srcs) * channels * 256 entries")
+        keep = [np.ascontiguousarray(s) for s in srcs]
+        sa = (ctypes.c_void_p * n)(*[_addr(s) if s.size else None for s in keep])
+        na = (ctypes.c_size_t * n)(*[int(s.nbytes) for s in keep])
+        self._check(self._lib.vf_hist_frames_host(self._ctx, sa, na, n, channels, hists.ctypes.data))
+
+    def hist_device(self, dsrc: int, nbytes: int, channels: int, dhist: int, stream: int = 0) -> None:
+        self._check(self._lib.vf_hist_device(self._ctx, dsrc or None, nbytes, channels, dhist or None, stream or None))
+
+    def level_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                          channels: int, rule: int, mask: int = 0, link: int = 0, clip_lo: int = 0,
+                          clip_hi: int = 0) -> None:
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
+        self._check(self._lib.vf_level_frames_host(self._ctx, sa, da, wa, ha, n, channels, rule, mask, link, clip_lo,
+                                                   clip_hi))
+
+    def level_device(self, dsrc: int, ddst: int, width: int, height: int, channels: int, rule: int, mask: int = 0,
+                     link: int = 0, clip_lo: int = 0, clip_hi: int = 0, stream: int = 0) -> None:
+        self._check(self._lib.vf_level_device(self._ctx, dsrc or None, ddst or None, width, height, channels, rule, mask,
+                                              link, clip_lo, clip_hi, stream or None))
+
     # -- filter chains (vf_chain_*, vf_binary_device) ------------------------------------------------
     def _steps(self, steps: Sequence):
         """``steps`` -- ``filters.Chain.args[0]``: tuples ``(kind, a, b, op, data, shift, border)`` with
@@ -600,6 +643,10 @@ class Context:
                 kx, ky, divisor = data
                 st.kw, st.kh = len(kx), len(ky)
                 d = np.concatenate([[divisor], self._taps(kx), self._taps(ky)]).astype(np.int32)
+            elif kind == STEP_LEVEL:  # data: (mask, link, clip_lo, clip_hi); op: the rule
+                d = np.array([int(v) for v in data], np.int32)
+                if d.shape != (4,):
+                    raise ValueError("a level step's data is (mask, link, clip_lo, clip_hi)")
             else:
                 d = None
             if d is not None:
@@ -1110,6 +1157,35 @@ class Context:
         the total, not in a stage, as ``jpeg_bench_conv``'s)."""
         return self._jpeg_bench(self._lib.vf_jpeg_bench_sep, self._taps_args(kx, ky, shift, divisor, rounding, border),
                                 "color", jpegs, quality, subsamp, flags, iters)
+
+    # -- JPEG with the level filter in place of the inversion (vf_jpeg_level*); tickets are invert tickets ----
+    def jpeg_level(self, jpegs: Sequence, rule: int, mask: int, link: int, clip_lo: int, clip_hi: int, quality: int,
+                   subsamp: int, flags: int = 0) -> list:
+        """decode -> cv2.equalizeHist / auto-levels -> encode for every JPEG on the GPU, each frame by its own
+        histogram; returns bytes."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_level_submit(jpegs, rule, mask, link, clip_lo, clip_hi, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_level_submit(self, jpegs: Sequence, rule: int, mask: int, link: int, clip_lo: int, clip_hi: int,
+                          quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the level filter; collect with the ``jpeg_invert_result*`` methods."""
+        return self._jpeg_submit("jpeg_level_submit", self._lib.vf_jpeg_level_submit,
+                                 (rule, mask, link, clip_lo, clip_hi), jpegs, None, quality, subsamp, flags)
+
+    def jpeg_level_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, rule: int, mask: int, link: int,
+                                clip_lo: int, clip_hi: int, quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_level_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        return self._jpeg_submit("jpeg_level_submit_addrs", self._lib.vf_jpeg_level_submit,
+                                 (rule, mask, link, clip_lo, clip_hi), addrs, sizes, quality, subsamp, flags)
+
+    def jpeg_bench_level(self, jpegs: Sequence, rule: int, mask: int, link: int, clip_lo: int, clip_hi: int,
+                         quality: int, subsamp: int, flags: int = 0, iters: int = 10):
+        """``jpeg_bench_invert`` with the level filter between the decode and the encode (its time is in the
+        total, not in a stage, as ``jpeg_bench_conv``'s)."""
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_level, (rule, mask, link, clip_lo, clip_hi), "color", jpegs,
+                                quality, subsamp, flags, iters)
 
     # -- JPEG with a filter chain in place of the inversion (vf_jpeg_chain*); tickets are invert tickets ----
     def jpeg_chain(self, jpegs: Sequence, steps: Sequence, quality: int, subsamp: int, flags: int = 0) -> list:

@@ -782,11 +782,166 @@ def sep_frames(frames: Sequence, sep: Separable, outs: Optional[List] = None, ct
                         lambda *a: (ctx or get_context()).sep_frames_host(*a, *sep.args))
 
 
+# -- level filter: cv2.equalizeHist, auto-levels, and the histogram --------------------------------------
+
+LEVEL_RULES = {"equalize": 0, "stretch": 1}  # VF_LEVEL_* (include/vfilter.h)
+LEVEL_MAX_CLIP = 32767  # in units of 1 / 65536 of the pixels (csrc/vf_level_plan.h kMaxClip)
+
+
+def _level_clip(clip) -> tuple:
+    """``clip`` -- a fraction in ``[0, 0.5)``, or ``(lo, hi)`` of them -- as the two integer clips."""
+    try:
+        lo, hi = (clip, clip) if np.ndim(clip) == 0 else clip
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"Level: clip is a fraction or (lo, hi), not {clip!r}") from None
+    out = []
+    for f in (lo, hi):
+        if not 0.0 <= f < 0.5:  # a NaN fails this too
+            raise ValueError(f"Level: clip = {f!r}; a clip is a fraction in [0, 0.5)")
+        q = int(round(f * 65536))
+        if q > LEVEL_MAX_CLIP:
+            raise ValueError(f"Level: clip = {f!r} is {q} / 65536; at most {LEVEL_MAX_CLIP} / 65536")
+        out.append(q)
+    return tuple(out)
+
+
+def _level_mask(channels) -> int:
+    """``channels`` -- ``None`` (all of the frame's) or channel indices among 0, 1, 2 -- as the mask's bits."""
+    if channels is None:
+        return 0
+    try:
+        chans = [channels] if np.ndim(channels) == 0 else list(channels)
+        if any(isinstance(c, bool) or int(c) != c for c in chans):
+            raise TypeError
+        chans = [int(c) for c in chans]
+    except (TypeError, ValueError):
+        raise ValueError(f"Level: channels is None or channel indices, not {channels!r}") from None
+    if not chans or any(c < 0 or c > 2 for c in chans) or len(set(chans)) != len(chans):
+        raise ValueError(f"Level: channels = {channels!r}; distinct indices among 0, 1, 2, at least one")
+    return sum(1 << c for c in chans)
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Level:
+    """A table made from the frame itself: per frame the histogram of each channel, from it a 256-entry
+    table by ``rule``, and the table applied.  ``rule`` "equalize" is ``cv2.equalizeHist``'s table;
+    "stretch" maps the range left after clipping the fractions ``clip`` (``(lo, hi)`` or one for both, in
+    ``[0, 0.5)``, kept as ``round(f * 65536)``) of the darkest and brightest pixels onto 0..255, rounding half
+    up; ``clip=0`` is min-max normalisation.  ``channels`` names the channels that are levelled (``None``:
+    all; the others pass unchanged); with ``link`` they share one table made from the sum of their
+    histograms, which keeps the hue.  ``Level.equalize`` and ``Level.stretch`` are the two rules' builders."""
+    rule: str
+    rule_code: int
+    mask: int
+    link: bool
+    clip_lo: int
+    clip_hi: int
+    family = "level"
+
+    def __init__(self, rule: str, clip=0.0, channels=None, link: bool = False):
+        if rule not in LEVEL_RULES:
+            raise ValueError(f"Level: rule must be one of {sorted(LEVEL_RULES)}, not {rule!r}")
+        lo, hi = _level_clip(clip)
+        if rule == "equalize" and (lo or hi):
+            raise ValueError("Level: the equalize rule takes no clip")
+        if not isinstance(link, (bool, np.bool_)):
+            raise ValueError(f"Level: link is a bool, not {link!r}")
+        fields = {"rule": rule, "rule_code": LEVEL_RULES[rule], "mask": _level_mask(channels), "link": bool(link),
+                  "clip_lo": lo, "clip_hi": hi}
+        for name, v in fields.items():
+            object.__setattr__(self, name, v)
+
+    @classmethod
+    def equalize(cls, channels=None, link: bool = False) -> "Level":
+        """``cv2.equalizeHist`` per channel (``link``: one table from the masked channels' summed histograms)."""
+        return cls("equalize", 0.0, channels, link)
+
+    @classmethod
+    def stretch(cls, clip=0.0, channels=None, link: bool = False) -> "Level":
+        """Auto-levels: the clipped range onto 0..255."""
+        return cls("stretch", clip, channels, link)
+
+    @property
+    def min_channels(self) -> int:
+        """3 when ``channels`` names channel 1 or 2 (such a filter takes 3-channel frames only), else 1."""
+        return 3 if self.mask >> 1 else 1
+
+    @property
+    def args(self) -> tuple:
+        return self.rule_code, self.mask, int(self.link), self.clip_lo, self.clip_hi
+
+
+def _level_frame(name: str, a, level: Level) -> np.ndarray:
+    a = _conv_frame(name, a)
+    if level.min_channels == 3 and (a.ndim != 3 or a.shape[2] != 3):
+        raise ValueError(f"{name}: the filter names channel 1 or 2; frames are H x W x 3, not shape {a.shape}")
+    return a
+
+
+def _level_one(name: str, src, level: Level, dst, ctx) -> np.ndarray:
+    src = np.ascontiguousarray(_level_frame(name, src, level))
+    dst = _rank_dst(name, src, dst)
+    channels = 1 if src.ndim == 2 else src.shape[2]
+    if src.size:
+        (ctx or get_context()).level_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, *level.args)
+    return dst
+
+
+def _hist_frames(name: str, frames: Sequence) -> tuple:
+    srcs = [np.ascontiguousarray(_conv_frame(name, f)) for f in frames]
+    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
+    if len(chans) > 1:
+        raise ValueError(f"{name}: the frames of one call have one channel count")
+    return srcs, (chans.pop() if chans else 1)
+
+
+def calc_hist(src: np.ndarray, ctx: Optional[Context] = None) -> np.ndarray:
+    """The histogram of a uint8 ``H x W`` or ``H x W x 3`` frame, counted on the GPU: a ``(channels, 256)`` uint32
+    array, ``[c, v]`` the pixels whose channel ``c`` is ``v`` -- ``cv2.calcHist([src], [c], None, [256], [0, 256])``
+    for every channel, as integers.  A frame larger than the context's staging is counted in pieces."""
+    return calc_hist_frames([src], ctx)[0]
+
+
+def calc_hist_frames(frames: Sequence, ctx: Optional[Context] = None) -> List:
+    """``calc_hist`` of separately stored frames of one channel count and mixed sizes in one call."""
+    srcs, channels = _hist_frames("calc_hist_frames", frames)
+    if not srcs:
+        return []
+    hists = np.zeros((len(srcs), channels, 256), np.uint32)
+    (ctx or get_context()).hist_frames_host(srcs, channels, hists)
+    return list(hists)
+
+
+def equalize_hist(src: np.ndarray, dst: Optional[np.ndarray] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.equalizeHist(src)`` on uint8 ``H x W`` input, bit-exact.  On ``H x W x 3`` every channel is
+    equalised by its own histogram: ``cv2.merge([cv2.equalizeHist(c) for c in cv2.split(src)])``.  ``dst`` as
+    for ``lut``, and it may be ``src``."""
+    return _level_one("equalize_hist", src, Level.equalize(), dst, ctx)
+
+
+def auto_levels(src: np.ndarray, clip=0.0, link: bool = False, dst: Optional[np.ndarray] = None,
+                ctx: Optional[Context] = None) -> np.ndarray:
+    """Auto-contrast: ``Level.stretch(clip, link=link)`` on a uint8 ``H x W`` or ``H x W x 3`` frame.  ``dst`` as for
+    ``lut``, and it may be ``src``."""
+    return _level_one("auto_levels", src, Level.stretch(clip, None, link), dst, ctx)
+
+
+def level_frames(frames: Sequence, level: Level, outs: Optional[List] = None, ctx: Optional[Context] = None) -> List:
+    """A ``Level`` over separately stored frames of one channel count and mixed sizes in one call, each frame by
+    its own histogram.  Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
+    if not isinstance(level, Level):
+        raise ValueError("level_frames: level is a Level")
+    return _frames_call("level_frames", [_level_frame("level_frames", f, level) for f in frames], outs,
+                        lambda *a: (ctx or get_context()).level_frames_host(*a, *level.args))
+
+
 # -- filter chains: a program of filters between one upload and one download ----------------------
 
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
 STEP_MIX = 5  # VF_STEP_MIX: 4 names no kind and stays refused
 STEP_SEP = 7  # VF_STEP_SEP: 6 stays refused as well
+STEP_LEVEL = 8  # VF_STEP_LEVEL: 9 stays refused as well
 BINARY_OPS = {"subtract": 0, "add": 1, "absdiff": 2, "min": 3, "max": 4}  # VF_BIN_*
 CHAIN_MAX_STEPS = 8  # VF_CHAIN_MAX_STEPS
 MORPH_OPS = ("erode", "dilate", "open", "close", "gradient", "tophat", "blackhat")
@@ -799,7 +954,7 @@ class Combine:
     """A two-input step of a ``Chain``: ``op(a, b)`` per byte, ``op`` one of "subtract"
     (``max(a - b, 0)``), "add" (``min(a + b, 255)``), "absdiff", "min", "max" -- ``cv2.subtract``,
     ``cv2.add``, ``cv2.absdiff``, ``cv2.min``, ``cv2.max`` on uint8.  ``a`` and ``b`` are each a filter
-    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``, another ``Combine``), a ``Chain``, or ``None``
+    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``, ``Level``, another ``Combine``), a ``Chain``, or ``None``
     for the value entering the ``Combine``; both are applied to that value."""
     op: str
     op_code: int
@@ -830,7 +985,9 @@ def _unary_step(f, a: int) -> tuple:
         return (STEP_MIX, a, 0, f.rounding_code, f.matrix, f.shift, 0)
     if isinstance(f, Separable):
         return (STEP_SEP, a, 0, f.rounding_code, (f.kx, f.ky, f.divisor), f.shift, f.border_code)
-    raise ValueError("chain: a step is Invert, Table, Kernel, Rank, Mix, Separable, Combine or Chain, "
+    if isinstance(f, Level):
+        return (STEP_LEVEL, a, 0, f.rule_code, (f.mask, int(f.link), f.clip_lo, f.clip_hi), 0, 0)
+    raise ValueError("chain: a step is Invert, Table, Kernel, Rank, Mix, Separable, Level, Combine or Chain, "
                      f"not {type(f).__name__}")
 
 
@@ -862,8 +1019,10 @@ class Chain:
     decode and one encode (JPEG): exactly what running its steps one after the other on whole frames
     gives, every step with whole-frame borders.
 
-    ``Chain(steps)``: each of ``steps`` -- ``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Combine`` or a
-    nested ``Chain``, which is flattened -- is applied to the result of the one before.
+    ``Chain(steps)``: each of ``steps`` -- ``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``,
+    ``Level``, ``Combine`` or a nested ``Chain``, which is flattened -- is applied to the result of the one
+    before.  A chain with a ``Level`` reads whole frames: a frame larger than the context's staging is
+    refused, not cut into bands.
     ``Chain.program(entries)`` takes the program itself: value 0 is the frame, value i the result of
     entry i (1-based); an entry is ``(filter value, a)`` or ``(binary op name, a, b)`` with ``a`` and
     ``b`` earlier values.  At most 8 steps; every value but the last is read.  A bad program raises
@@ -912,11 +1071,16 @@ class Chain:
         """True when a step is a colour matrix (such a chain takes 3-channel frames only)."""
         return any(st[0] == STEP_MIX for st in self.steps)
 
+    @property
+    def level_channels(self) -> int:
+        """3 when a level step names channel 1 or 2 (such a chain takes 3-channel frames only), else 1."""
+        return 3 if any(st[0] == STEP_LEVEL and st[4][0] >> 1 for st in self.steps) else 1
+
     def __len__(self) -> int:
         return len(self.steps)
 
 
-_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable)
+_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable, Level)
 
 
 def _lower(item, cur: int, prog: List[tuple]) -> int:
@@ -982,6 +1146,8 @@ def _chain_frame(name: str, a, c: Chain) -> np.ndarray:
         raise ValueError(f"{name}: the chain has a 3-channel table; frames are H x W x 3, not shape {a.shape}")
     if c.has_mix and (a.ndim != 3 or a.shape[2] != 3):
         raise ValueError(f"{name}: the chain has a colour matrix; frames are H x W x 3, not shape {a.shape}")
+    if c.level_channels == 3 and (a.ndim != 3 or a.shape[2] != 3):
+        raise ValueError(f"{name}: a level step names channel 1 or 2; frames are H x W x 3, not shape {a.shape}")
     return a
 
 

@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import Invert, Kernel, Morph, Rank, Separable, Table, _as_chain, _as_mix
+from .filters import Invert, Kernel, Level, Morph, Rank, Separable, Table, _as_chain, _as_mix
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -94,7 +94,7 @@ class TurboJPEG:
         return self.ctx.jpeg_encode(list(imgs), pixel_format, quality, jpeg_subsample,
                                     self._enc_flags(flags, quality))
 
-    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank, Mix, Separable, Chain) between decode and encode.  The
+    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank, Mix, Separable, Level, Chain) between decode and encode.  The
     # ``invert*``, ``lut*`` and ``filter2d*`` methods below are these three with their filter built
     # from the call's own arguments.
     def filter_batch(self, jpeg_bufs: Sequence, filt, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
@@ -252,6 +252,26 @@ class TurboJPEG:
     def blur_batch(self, jpeg_bufs: Sequence, ksize, border: str = "reflect101", quality: int = 85,
                    jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
         return self.filter_batch(jpeg_bufs, Separable.box(ksize, True, border), quality, jpeg_subsample, flags)
+
+    # -- the level filter: cv2.equalizeHist / auto-levels between decode and encode ------------------------
+    # The submit forms go through ``filter_batch_submit*`` with a ``vfilter.filters.Level``.
+    def equalize_hist(self, jpeg_buf, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(equalize(decode(jpeg_buf)))`` on the GPU, the pixels never leaving it: every channel of the
+        decoded BGR frame through ``cv2.equalizeHist`` by its own histogram."""
+        return self.filter_batch([jpeg_buf], Level.equalize(), quality, jpeg_subsample, flags)[0]
+
+    def equalize_hist_batch(self, jpeg_bufs: Sequence, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                            flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, Level.equalize(), quality, jpeg_subsample, flags)
+
+    def auto_levels(self, jpeg_buf, clip=0.0, link: bool = False, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
+                    flags: int = 0) -> bytes:
+        """``encode(vfilter.auto_levels(decode(jpeg_buf), clip, link))`` on the GPU."""
+        return self.filter_batch([jpeg_buf], Level.stretch(clip, None, link), quality, jpeg_subsample, flags)[0]
+
+    def auto_levels_batch(self, jpeg_bufs: Sequence, clip=0.0, link: bool = False, quality: int = 85,
+                          jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, Level.stretch(clip, None, link), quality, jpeg_subsample, flags)
 
     # -- a filter chain (vfilter.filters.Chain) between one decode and one encode ------------------------
     def chain(self, jpeg_buf, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:

@@ -525,6 +525,74 @@ int vf_jpeg_bench_sep(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jp
                       int rounding, int border, int quality, int subsamp, int flags, int iters,
                       float *ms, float *stage_ms);
 
+/* ---- level filter (cv2.equalizeHist, auto-levels) and the histogram ---------------------------
+ * For uint8 frames of 1 or 3 interleaved channels, bit-exact.  Per frame: the
+ * histogram of the frame, hist[c][v] = the bytes of channel c equal to v, as uint32; from it a
+ * 256-entry table per channel by a fixed rule; the table applied.  A frame has at most 2^32 - 1
+ * pixels.
+ *   rule     VF_LEVEL_EQUALIZE: cv2.equalizeHist's table of a histogram h with `total` entries:
+ *              i0 the first v with h[v] != 0; the identity when h[i0] == total; else
+ *              scale = 255.0f / (float)(total - h[i0]), table[v] = 0 for v <= i0 and
+ *              clamp(rint((float)(h[i0 + 1] + .. + h[v]) * scale), 0, 255) above, in IEEE single
+ *              precision, every operation rounded to nearest even.
+ *            VF_LEVEL_STRETCH: in integers, cut_lo = (total * clip_lo) >> 16, cut_hi likewise;
+ *              lo the smallest v with h[0] + .. + h[v] > cut_lo, hi the largest v with
+ *              h[v] + .. + h[255] > cut_hi; the identity when hi <= lo; else table[v] = 0 for
+ *              v <= lo, 255 for v >= hi, (510 (v - lo) + (hi - lo)) / (2 (hi - lo)) between.
+ *   mask     bits 0..2: the channels that are levelled, the others pass unchanged; 0: all of the
+ *            frame's channels; a bit beyond the frame's channel count is refused.
+ *   link     0: each masked channel its own table from its own histogram; 1: one table for all
+ *            masked channels from the sum of their histograms (total: the sum of their pixel
+ *            counts, which must fit 32 bits as well).
+ *   clip_lo, clip_hi   0 .. 32767, in units of 1 / 65536 of the total; the stretch rule's, and 0
+ *            for equalize.
+ * Anything else is VF_E_INVALID with the reason, before any GPU work.  The empty frame is a no-op. */
+#define VF_LEVEL_EQUALIZE 0
+#define VF_LEVEL_STRETCH  1
+
+/* Enqueue the histogram of `nbytes` device bytes (whole pixels: nbytes % channels == 0) on
+ * `stream`: dhist, channels * 256 uint32 in device memory (4-byte aligned), is zeroed and
+ * counted into.  Any alignment of dsrc; returns after the launch. */
+int vf_hist_device(vf_ctx *ctx, const void *dsrc, size_t nbytes, int channels, uint32_t *dhist,
+                   void *stream);
+
+/* The histograms of `n` separately allocated host frames of mixed sizes, synchronous: hists
+ * receives n * channels * 256 host uint32, frame i's at i * channels * 256.  A frame larger than
+ * the context's staging is counted over several fills.  Each nbytes[i] % channels == 0. */
+int vf_hist_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, const size_t *nbytes, int n,
+                        int channels, uint32_t *hists);
+
+/* Enqueue the filter on `stream` over one device-resident frame: any alignment, ddst == dsrc
+ * allowed (the histogram is complete before the first byte is written), a partial overlap is
+ * not; returns after the launches.  The histogram words are the context's: calls on one context
+ * that may run at the same time on different streams need a context each. */
+int vf_level_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                    int rule, int mask, int link, int clip_lo, int clip_hi, void *stream);
+
+/* The filter on `n` separately allocated host frames of mixed sizes, synchronous; srcs[i] ==
+ * dsts[i] is allowed.  A frame that does not fit the context's staging whole is refused: the
+ * table needs the whole frame, so a frame is never cut into bands. */
+int vf_level_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                         const int *widths, const int *heights, int n, int channels, int rule,
+                         int mask, int link, int clip_lo, int clip_hi);
+
+/* vf_jpeg_invert with the filter in place of the inversion: decode -> level -> encode on the GPU,
+ * on the decoded 3-channel BGR frame (grayscale inputs included), each frame from its own
+ * histogram. */
+int vf_jpeg_level(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                  int rule, int mask, int link, int clip_lo, int clip_hi, int quality, int subsamp,
+                  int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the filter.  The ticket is an invert ticket. */
+int vf_jpeg_level_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                         int rule, int mask, int link, int clip_lo, int clip_hi, int quality,
+                         int subsamp, int flags, uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the filter between the decode and the encode. */
+int vf_jpeg_bench_level(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                        int rule, int mask, int link, int clip_lo, int clip_hi, int quality,
+                        int subsamp, int flags, int iters, float *ms, float *stage_ms);
+
 /* ---- filter chains (cv2.morphologyEx, difference of blurs, ...) -----------------------------
  * A program is a straight-line list of 1 .. VF_CHAIN_MAX_STEPS steps over values.
  * Value 0 is the input frame (uint8, 1 or 3 interleaved channels, packed rows), value i the result
@@ -542,18 +610,23 @@ int vf_jpeg_bench_sep(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jp
  *                   `op` a VF_ROUND_*; 3-channel frames only
  *   VF_STEP_SEP     the separable filter: `data` is 1 + kw + kh int32, the divisor (0 or 1: none),
  *                   then kx, then ky; `kw`, `kh` the tap counts, `shift`, `op` a VF_ROUND_*, `border`
+ *   VF_STEP_LEVEL   the level filter: `op` a VF_LEVEL_*, `data` 4 int32 {mask, link, clip_lo, clip_hi}.
+ *                   It reads its whole operand, so a program that holds one runs on whole frames
+ *                   only: vf_chain_frames_host refuses a frame that does not fit the staging whole
  * `data` is a HOST pointer, read during the call only.  VF_E_INVALID, before any GPU work: a step
  * that reads a later value or itself, a value other than the last that no step reads, a 3-channel
  * table or a colour matrix on 1-channel frames, more than VF_CHAIN_MAX_STEPS steps, and anything
  * the single-filter entry points refuse for a table, a kernel, an element or a matrix.
  * The VF_STEP_* values are not dense: 4 names no kind and stays refused ("unknown kind 4"), as
- * callers' checks of the refusal expect, so VF_STEP_MIX is 5; 6 likewise, so VF_STEP_SEP is 7. */
+ * callers' checks of the refusal expect, so VF_STEP_MIX is 5; 6 likewise, so VF_STEP_SEP is 7 and
+ * VF_STEP_LEVEL 8; 9 stays refused too. */
 #define VF_STEP_TABLE  0
 #define VF_STEP_CONV   1
 #define VF_STEP_RANK   2
 #define VF_STEP_BINARY 3
 #define VF_STEP_MIX    5
 #define VF_STEP_SEP    7
+#define VF_STEP_LEVEL  8
 #define VF_BIN_SUBTRACT 0
 #define VF_BIN_ADD      1
 #define VF_BIN_ABSDIFF  2
@@ -564,9 +637,9 @@ int vf_jpeg_bench_sep(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jp
 typedef struct vf_step {
   int kind;         /* a VF_STEP_* */
   int a, b;         /* operand values; b for VF_STEP_BINARY only */
-  int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_*; VF_STEP_MIX, VF_STEP_SEP: a VF_ROUND_* */
-  const void *data; /* the table, the int16 weights, the element or the int32 of a matrix or of
-                       separable taps (host memory) */
+  int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_*; VF_STEP_MIX, VF_STEP_SEP: a VF_ROUND_*; VF_STEP_LEVEL: a VF_LEVEL_* */
+  const void *data; /* the table, the int16 weights, the element or the int32 of a matrix, of
+                       separable taps or of a level step (host memory) */
   int kw, kh;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP */
   int shift;        /* VF_STEP_CONV, VF_STEP_MIX, VF_STEP_SEP */
   int border;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP: a VF_BORDER_* */
