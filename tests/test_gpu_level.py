@@ -6,7 +6,8 @@ Sizes: the stream kernels' tile is 256 lanes x 4 vectors x 16 B = 16 KiB, so 480
 42 whole tiles and a partial one over several workgroups, 250 x 130 a few, and the small frames only
 the head, tail and partial-tile paths.  ``stream::chunks`` cuts a launch only above 512 MiB of body,
 which no test of a few MB reaches: that boundary is covered by ``tests/stream/stream_split_check.cc``
-on the CPU, not here.
+on the CPU, not here.  No frame here has more tiles than the grid's cap; the strided grid, a
+workgroup's second and later tiles, is covered in ``tests/test_gpu_grid_stride.py``.
 """
 import ctypes
 
