@@ -1314,7 +1314,7 @@ int header_info(const uint8_t *jpeg, size_t size, int *w, int *h, int *subsamp, 
   *w = P.w;
   *h = P.h;
   *subsamp = subsamp_of(P);
-  *colorspace = P.ncomp == 1 ? 2 : 1;  // TJCS_GRAY = 2, TJCS_YCbCr = 1
+  *colorspace = P.ncomp == 1 ? 2 : P.rgb ? 0 : 1;  // TJCS_GRAY = 2, TJCS_RGB = 0 (not decoded), TJCS_YCbCr = 1
   return kOk;
 }
 

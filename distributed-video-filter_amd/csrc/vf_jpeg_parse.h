@@ -236,6 +236,12 @@ struct Parsed {
   uint8_t dcvals[4][256] = {}, acvals[4][256] = {};
   int qdef = 0, dcdef = 0, acdef = 0;
   size_t scan_off = 0, scan_end = 0;
+  // colour space by libjpeg's rule (jdapimin.c default_decompress_parms), set at SOS: a JFIF
+  // APP0 seen -> YCbCr; else an Adobe APP14 -> its transform byte (0 = RGB, anything else
+  // YCbCr); else component ids 'R','G','B' -> RGB, anything else YCbCr.  One component is gray.
+  bool jfif = false;
+  int adobe = -1;  // the Adobe marker's transform byte, -1 without one
+  bool rgb = false;
   // with DRI: each RSTn marker in the scan as (end of the interval's data before it, marker
   // number); the next interval starts 2 bytes after the data end plus any fill bytes
   std::vector<std::pair<size_t, size_t>> rst;  // (data end, position of the marker's 0xFF)
@@ -306,6 +312,10 @@ inline int parse(const uint8_t *b, size_t n, Parsed *P, std::string *err, bool f
       sof = true;
     } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
       return fail("progressive / lossless / arithmetic JPEG is not supported");
+    } else if (m == 0xE0) {  // jdmarker.c examine_app0: 14 data bytes, "JFIF\0"
+      if (len >= 16 && std::memcmp(s, "JFIF", 5) == 0) P->jfif = true;
+    } else if (m == 0xEE) {  // examine_app14: 12 data bytes, "Adobe"; the last marker's transform holds
+      if (len >= 14 && std::memcmp(s, "Adobe", 5) == 0) P->adobe = s[11];
     } else if (m == 0xDD) {
       if (len != 4) return fail("bad DRI");
       P->restart = (s[0] << 8) | s[1];
@@ -347,6 +357,8 @@ inline int parse(const uint8_t *b, size_t n, Parsed *P, std::string *err, bool f
       for (int c = 0; c < P->ncomp; ++c)
         if (!(P->qdef >> P->tq[c] & 1) || !(P->dcdef >> P->td[c] & 1) || !(P->acdef >> P->ta[c] & 1))
           return fail("scan refers to an undefined table");
+      P->rgb = P->ncomp == 3 && !P->jfif &&
+               (P->adobe >= 0 ? P->adobe == 0 : P->id[0] == 'R' && P->id[1] == 'G' && P->id[2] == 'B');
       return 0;
     }
     p += len;
@@ -504,6 +516,11 @@ inline bool parse_frame(const uint8_t *jpeg, size_t size, uint64_t max_pixels, P
     return false;
   }
   if (parse(jpeg, size, P, err) != 0) return false;
+  if (P->rgb) {  // decoded as YCbCr it would be a wrong picture, not an error
+    *err = "JPEG in the RGB colour space (Adobe transform 0, or component ids R, G, B without a JFIF marker) is not "
+           "supported: only YCbCr and grayscale are";
+    return false;
+  }
   if (!check_frame_size(*P, max_pixels, err)) return false;
   if (!make_geom(P->w, P->h, P->ncomp, P->hs, P->vs, g)) {
     *err = "unsupported sampling geometry";

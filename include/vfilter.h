@@ -223,7 +223,8 @@ int vf_bench_device_ring(vf_ctx *ctx, void *const *srcs, void *const *dsts, int 
 #define VF_TJFLAG_ACCURATEDCT 4096   /* accepted; islow is the default */
 
 /* Header of one JPEG, no GPU work (replaces TurboJPEG.decode_header).  *subsamp = TJSAMP_*
- * (-1 if none matches), *colorspace = TJCS_YCbCr (1) or TJCS_GRAY (2). */
+ * (-1 if none matches), *colorspace = TJCS_YCbCr (1), TJCS_GRAY (2), or TJCS_RGB (0) for a
+ * three-component stream libjpeg reads as RGB, which the decode calls refuse. */
 int vf_jpeg_header(const uint8_t *jpeg, size_t size, int *width, int *height, int *subsamp,
                    int *colorspace);
 

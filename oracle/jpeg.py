@@ -143,6 +143,10 @@ def _x():
         lib.xc_encode.restype = sz
         lib.xc_encode_ex.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, sz]
         lib.xc_encode_ex.restype = sz
+        lib.xc_encode_factors.argtypes = [vp, ci, ci, ci, ci, ctypes.POINTER(ci), ci, ci, ci, ci, ci, vp, sz]
+        lib.xc_encode_factors.restype = sz
+        lib.xc_colorspace.argtypes = [vp, sz]
+        lib.xc_colorspace.restype = ci
         lib.xc_decode.argtypes = [vp, sz, ci, ci, ci, ci, ci, vp]
         lib.xc_decode.restype = ci
         _xlib = lib
@@ -175,9 +179,49 @@ def libjpeg_encode(img: np.ndarray, quality: int = 85, pixel_format: int = TJPF_
     return out[:n].tobytes()
 
 
-def libjpeg_decode(jpeg, pixel_format: int = TJPF_BGR, fast_upsample: bool = False) -> np.ndarray:
+def blocks_per_mcu(factors) -> int:
+    """Blocks in one interleaved MCU of a three-component frame with sampling factors
+    (h0, v0, h1, v1, h2, v2); libjpeg allows at most 10 (D_MAX_BLOCKS_IN_MCU)."""
+    return sum(factors[2 * k] * factors[2 * k + 1] for k in range(3))
+
+
+def libjpeg_encode_factors(img: np.ndarray, quality: int, factors, *, colorspace: str = "ycc",
+                           jfif: bool = True, adobe: bool = False, restart_interval: int = 0,
+                           optimize: bool = False) -> bytes:
+    """libjpeg-turbo with the six per-component sampling factors (h0, v0, h1, v1, h2, v2) set
+    directly: the layouts TJSAMP_* cannot name.  ``colorspace="rgb"`` leaves the samples
+    untransformed (component ids 'R','G','B'); ``jfif`` / ``adobe`` choose the APP0 / APP14
+    markers.  Raises ValueError where libjpeg refuses the layout (over 10 blocks per MCU)."""
+    if colorspace not in ("ycc", "rgb") or len(factors) != 6:
+        raise ValueError("colorspace is 'ycc' or 'rgb'; factors are (h0, v0, h1, v1, h2, v2)")
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w = img.shape[:2]
+    cap = 3 * (w + 32) * (h + 32) * 2 + 2 * (w * h // 64 + 16) + 65536
+    out = np.empty(cap, np.uint8)
+    ok, why = libjpeg_available()
+    if not ok:
+        raise RuntimeError("libjpeg-turbo not usable: " + why)
+    f = (ctypes.c_int * 6)(*[int(v) for v in factors])
+    n = _x().xc_encode_factors(img.ctypes.data, w, h, 1, quality, f, int(colorspace == "rgb"), int(jfif),
+                               int(adobe), restart_interval, int(optimize), out.ctypes.data, cap)
+    if n == 0:
+        raise ValueError(f"libjpeg refuses sampling factors {tuple(factors)}")
+    return out[:n].tobytes()
+
+
+def libjpeg_colorspace(jpeg) -> str:
+    """The colour space libjpeg-turbo's jpeg_read_header assigns the stream: 'gray', 'rgb', 'ycc'."""
     a = _buf(jpeg)
-    hdr = info(a)
+    cs = _x().xc_colorspace(a.ctypes.data, a.nbytes)
+    if cs not in (1, 2, 3):
+        raise RuntimeError("libjpeg read_header failed: " + libjpeg_available()[1])
+    return {1: "gray", 2: "rgb", 3: "ycc"}[cs]
+
+
+def libjpeg_decode(jpeg, pixel_format: int = TJPF_BGR, fast_upsample: bool = False, hdr: Optional[dict] = None) -> np.ndarray:
+    """``hdr`` (width, height, ncomp) for a stream the oracle's own parse refuses."""
+    a = _buf(jpeg)
+    hdr = hdr or info(a)
     out = np.empty((hdr["height"], hdr["width"], 3), np.uint8)
     rc = _x().xc_decode(a.ctypes.data, a.nbytes, int(pixel_format == TJPF_BGR), int(fast_upsample),
                         hdr["width"], hdr["height"], hdr["ncomp"], out.ctypes.data)

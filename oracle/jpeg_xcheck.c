@@ -271,6 +271,98 @@ size_t xc_encode_ex(const uint8_t *img, int w, int h, int bgr, int quality, int 
   return result;
 }
 
+/* xc_encode_ex with the six sampling factors (h0, v0, h1, v1, h2, v2) written into comp_info
+ * as given, for layouts TurboJPEG's TJSAMP_* cannot name; rgb != 0 keeps the samples in the RGB
+ * colour space (jpeg_set_colorspace(JCS_RGB): component ids 'R','G','B', no colour transform);
+ * jfif / adobe choose the APP0 / APP14 markers written (jcmarker.c: the Adobe transform byte is
+ * 1 for YCbCr and 0 for RGB).  Returns 0 where libjpeg refuses (jcmaster.c initial_setup:
+ * more than 10 blocks per MCU, a factor outside 1..4). */
+size_t xc_encode_factors(const uint8_t *img, int w, int h, int bgr, int quality, const int factors[6], int rgb,
+                         int jfif, int adobe, int restart_interval, int optimize, uint8_t *out, size_t cap) {
+  if (!xc_available(NULL, 0)) return 0;
+  cinfo_t c;
+  memset(&c, 0, sizeof c);
+  c.err = new_err();
+  unsigned char *buf = NULL;
+  unsigned long size = 0;
+  size_t result = 0;
+  if (setjmp(g_jmp)) {
+    p_destroy(&c);
+    free(buf);
+    return 0;
+  }
+  p_CreateCompress(&c, JPEG_LIB_VERSION, sizeof c);
+  p_mem_dest(&c, &buf, &size);
+  c.image_width = (unsigned)w;
+  c.image_height = (unsigned)h;
+  c.input_components = 3;
+  c.in_color_space = bgr ? JCS_EXT_BGR : JCS_RGB;
+  p_set_defaults(&c);
+  if (c.data_precision != 8 || c.num_components != 3 || c.jpeg_color_space != JCS_YCbCr ||
+      c.write_JFIF_header != 1 || c.write_Adobe_marker != 0 || *(int *)(c.comp_info + 0) != 1 ||
+      *(int *)(c.comp_info + 8) != 2 || *(int *)(c.comp_info + 12) != 2) {
+    snprintf(g_why, sizeof g_why, "compress struct mirror does not match libjpeg's layout");
+    g_state = -1;
+    p_destroy(&c);
+    free(buf);
+    return 0;
+  }
+  p_set_quality(&c, quality, 1);
+  c.dct_method = JDCT_ISLOW;
+  p_set_colorspace(&c, rgb ? JCS_RGB : JCS_YCbCr);
+  if (c.write_JFIF_header != !rgb || c.write_Adobe_marker != !!rgb) { /* jcparam.c sets both per space */
+    snprintf(g_why, sizeof g_why, "compress struct mirror does not match libjpeg's layout (markers)");
+    g_state = -1;
+    p_destroy(&c);
+    free(buf);
+    return 0;
+  }
+  for (int k = 0; k < 3; ++k) {
+    *(int *)(c.comp_info + k * COMP_INFO_SIZE + 8) = factors[2 * k];
+    *(int *)(c.comp_info + k * COMP_INFO_SIZE + 12) = factors[2 * k + 1];
+  }
+  c.write_JFIF_header = jfif;
+  c.write_Adobe_marker = adobe;
+  c.restart_interval = (unsigned)restart_interval;
+  c.optimize_coding = optimize;
+  p_start_compress(&c, 1);
+  while (c.next_scanline < (unsigned)h) {
+    unsigned char *row = (unsigned char *)img + (size_t)c.next_scanline * w * 3;
+    p_write_scanlines(&c, &row, 1);
+  }
+  p_finish_compress(&c);
+  if (size <= cap) {
+    memcpy(out, buf, size);
+    result = size;
+  }
+  p_destroy(&c);
+  free(buf);
+  return result;
+}
+
+/* jpeg_read_header's verdict on the stream's colour space (jdmarker.c / jdapimin.c
+ * default_decompress_parms): JCS_GRAYSCALE 1, JCS_RGB 2, JCS_YCbCr 3; -1 on failure. */
+int xc_colorspace(const uint8_t *jpg, size_t n) {
+  static char dbuf[4096] __attribute__((aligned(16)));
+  if (!xc_available(NULL, 0)) return -1;
+  memset(dbuf, 0, sizeof dbuf);
+  *(void **)dbuf = new_err();
+  if (setjmp(g_jmp)) {
+    p_destroy(dbuf);
+    return -1;
+  }
+  p_CreateDecompress(dbuf, JPEG_LIB_VERSION, g_dsize);
+  p_mem_src(dbuf, jpg, (unsigned long)n);
+  p_read_header(dbuf, 1);
+  const int ncomp = *(int *)(dbuf + D_NUM_COMPONENTS);
+  int cs = *(int *)(dbuf + D_JPEG_COLOR_SPACE);
+  if (*(int *)(dbuf + D_OUT_COLOR_SPACE) != (ncomp == 3 ? JCS_RGB : JCS_GRAYSCALE) ||
+      *(int *)(dbuf + D_DCT_METHOD) != JDCT_ISLOW || *(int *)(dbuf + D_DO_FANCY_UPSAMPLING) != 1)
+    cs = -1; /* the offsets do not match this library */
+  p_destroy(dbuf);
+  return cs;
+}
+
 /* tjDecompress2(pixel_format BGR/RGB, flags) through libjpeg: w*h*3 bytes into `out`.
  * Returns 0 on success, -1 on failure. */
 int xc_decode(const uint8_t *jpg, size_t n, int bgr, int fast_upsample, int w, int h, int ncomp,

@@ -842,6 +842,7 @@ int vfo_jpeg_parse(const uint8_t *jpg, size_t n, vfo_jpeg_info *info) {
   if (n < 4 || jpg[0] != 0xFF || jpg[1] != 0xD8) return VFO_JE_NOT_JPEG;
   size_t p = 2;
   int have_sof = 0;
+  int saw_jfif = 0, adobe_transform = -1; /* jdmarker.c saw_JFIF_marker / saw_Adobe_marker + Adobe_transform */
   for (;;) {
     while (p < n && jpg[p] != 0xFF) p++; /* tolerate garbage between markers */
     while (p < n && jpg[p] == 0xFF) p++;
@@ -898,6 +899,10 @@ int vfo_jpeg_parse(const uint8_t *jpg, size_t n, vfo_jpeg_info *info) {
       have_sof = 1;
     } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
       return VFO_JE_UNSUPPORTED; /* progressive, lossless, arithmetic, hierarchical */
+    } else if (m == 0xE0) { /* examine_app0: at least 14 data bytes starting "JFIF\0" */
+      if (len >= 16 && memcmp(s, "JFIF", 5) == 0) saw_jfif = 1;
+    } else if (m == 0xEE) { /* examine_app14: at least 12 data bytes starting "Adobe" */
+      if (len >= 14 && memcmp(s, "Adobe", 5) == 0) adobe_transform = s[11];
     } else if (m == 0xDD) {
       if (len != 4) return VFO_JE_BAD;
       info->restart_interval = (s[0] << 8) | s[1];
@@ -931,6 +936,19 @@ int vfo_jpeg_parse(const uint8_t *jpg, size_t n, vfo_jpeg_info *info) {
         if (maxh % info->h[c] || maxv % info->v[c]) return VFO_JE_UNSUPPORTED;
       info->max_h = maxh;
       info->max_v = maxv;
+      if (info->ncomp == 3) {
+        /* jdinput.c per_scan_setup: JERR_BAD_MCU_SIZE above D_MAX_BLOCKS_IN_MCU = 10 */
+        int bpm = 0;
+        for (int c = 0; c < 3; ++c) bpm += info->h[c] * info->v[c];
+        if (bpm > 10) return VFO_JE_UNSUPPORTED;
+        /* jdapimin.c default_decompress_parms: JFIF -> YCbCr; else Adobe transform 0 -> RGB, any
+         * other -> YCbCr; else ids 'R','G','B' -> RGB, anything else YCbCr.  RGB is not restated. */
+        const int rgb = saw_jfif ? 0
+                        : adobe_transform >= 0
+                            ? adobe_transform == 0
+                            : info->comp_id[0] == 'R' && info->comp_id[1] == 'G' && info->comp_id[2] == 'B';
+        if (rgb) return VFO_JE_UNSUPPORTED;
+      }
       for (int c = 0; c < info->ncomp; ++c) {
         if (!(info->qt_defined >> info->tq[c] & 1) || !(info->dc_defined >> info->td[c] & 1) ||
             !(info->ac_defined >> info->ta[c] & 1))
