@@ -34,6 +34,7 @@
 #include "vf_internal.h"
 #include "vf_sep_plan.h"
 #include "vf_level_plan.h"
+#include "vf_clahe_plan.h"
 #include "vf_jpeg_codec.h"
 #include "vf_lut_split.h"
 #include "vf_conv_bands.h"
@@ -97,6 +98,11 @@ struct vf_ctx {
   uint32_t *level_hist = nullptr;
   std::mutex level_mu;
   uint32_t *level_dev_hist = nullptr;
+  // the same for a program with CLAHE steps (vf_clahe.hip): level_hist then holds
+  // chain::whole_frame_scratch_bytes of the program, level_hist_bytes what it holds now; clahe_dev
+  // is vf_clahe_device's clahe::kScratchBytes (level_mu guards its creation)
+  size_t level_hist_bytes = 0;
+  void *clahe_dev = nullptr;
 };
 
 namespace {
@@ -279,6 +285,7 @@ VF_EXPORT int vf_destroy(vf_ctx *ctx) {
     for (uint8_t *p : ctx->raw_scratch) (void)hipFree(p);
     if (ctx->level_hist) (void)hipFree(ctx->level_hist);
     if (ctx->level_dev_hist) (void)hipFree(ctx->level_dev_hist);
+    if (ctx->clahe_dev) (void)hipFree(ctx->clahe_dev);
     (void)hipStreamDestroy(ctx->raw_stream);
   }
   for (vf::jpeg::Codec *c : ctx->jpeg_all) delete c;  // each synchronises its stream first
@@ -578,6 +585,13 @@ hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const
       e = hist ? launch_level(a, dst, nbytes, channels, s.op, s.mask, s.link, s.clip_lo, s.clip_hi,
                               hist + (size_t)(l.step - 1) * level::kHistWords, cfg, stream)
                : hipErrorInvalidValue;
+    else if (s.kind == chain::kClahe)  // whole frames only as well: the operand is frame_h rows
+      e = hist && l.nrows == frame_h
+              ? launch_clahe(a, dst, w, frame_h, channels, s.clip_q8, s.tiles_x, s.tiles_y, s.mask,
+                             reinterpret_cast<uint8_t *>(hist) + chain::level_scratch_bytes() +
+                                 (size_t)chain::clahe_steps_before(prog, l.step) * clahe::kScratchBytes,
+                             stream)
+              : hipErrorInvalidValue;
     else
       e = hipErrorInvalidValue;  // no kernel for the kind: validate() lets none through
     if (e != hipSuccess) return e;
@@ -632,6 +646,10 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
         if (s.kind == vf::chain::kLevel &&
             !vf::level::pixels_ok((uint64_t)widths[i] * (uint64_t)heights[i], s.mask, s.link, channels, &why))
           return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
+      for (const vf::chain::Step &s : prog.steps)
+        if (s.kind == vf::chain::kClahe &&
+            !vf::clahe::frame_ok((uint64_t)widths[i], (uint64_t)heights[i], s.tiles_x, s.tiles_y, &why))
+          return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
       if (row * (size_t)heights[i] > cap)
         return set_err(ctx, VF_E_INVALID, 0,
                        "%s: frame %d: %d rows of %zu bytes do not fit the context's %zu-byte staging (a level step "
@@ -661,10 +679,14 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
     VF_HIP(ctx, hipMalloc(&p, alloc));
     ctx->raw_scratch.push_back(static_cast<uint8_t *>(p));
   }
-  if (whole && !ctx->level_hist) {
+  if (whole && ctx->level_hist_bytes < vf::chain::whole_frame_scratch_bytes(prog)) {
+    // nothing is queued on raw_stream between calls (each ends with a wait), so the old words are idle
+    if (ctx->level_hist) VF_HIP(ctx, hipFree(ctx->level_hist));
+    ctx->level_hist = nullptr, ctx->level_hist_bytes = 0;
     void *p = nullptr;
-    VF_HIP(ctx, hipMalloc(&p, (size_t)vf::chain::kMaxSteps * vf::level::kHistWords * sizeof(uint32_t)));
+    VF_HIP(ctx, hipMalloc(&p, vf::chain::whole_frame_scratch_bytes(prog)));
     ctx->level_hist = static_cast<uint32_t *>(p);
+    ctx->level_hist_bytes = vf::chain::whole_frame_scratch_bytes(prog);
   }
   uint8_t *base[vf::chain::kMaxSteps + 1] = {};  // base[0]: each piece's upload; a value per step at the most
   std::copy(ctx->raw_scratch.begin(), ctx->raw_scratch.end(), base + 1);
@@ -1031,7 +1053,61 @@ VF_EXPORT int vf_level_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint
   return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
 }
 
-// ---- filter chains: a program of table / conv / rank / binary / mix / sep / level steps on raw frames
+// ---- CLAHE (cv2.createCLAHE(...).apply) on raw frames ---------------------------------------------------
+
+namespace {
+
+// The filter arguments every vf_clahe_* / vf_jpeg_clahe* entry point and a VF_STEP_CLAHE step share
+// (vf_clahe_plan.h has the limits).
+int check_clahe(vf_ctx *ctx, const char *fn, int clip_q8, int tiles_x, int tiles_y, int mask, int channels) {
+  std::string why;
+  if (!vf::clahe::limits_ok(clip_q8, tiles_x, tiles_y, mask, channels, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  return VF_OK;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_clahe_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels, int clip_q8,
+                              int tiles_x, int tiles_y, int mask, void *stream) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_clahe_device";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_clahe(ctx, fn, clip_q8, tiles_x, tiles_y, mask, channels)) != VF_OK) return rc;
+  if (width == 0 && height == 0) return VF_OK;  // the empty frame
+  if ((rc = check_frame_shape(ctx, fn, width, height, channels)) != VF_OK) return rc;
+  std::string why;
+  if (!vf::clahe::frame_ok((uint64_t)width, (uint64_t)height, tiles_x, tiles_y, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL buffer", fn);
+  const size_t nbytes = (size_t)width * (size_t)channels * (size_t)height;
+  if (overlaps_partially((const uint8_t *)dsrc, (const uint8_t *)ddst, nbytes))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: src and dst partially overlap", fn);
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  {
+    std::lock_guard<std::mutex> lk(ctx->level_mu);
+    if (!ctx->clahe_dev) VF_HIP(ctx, hipMalloc(&ctx->clahe_dev, vf::clahe::kScratchBytes));
+  }
+  VF_HIP(ctx, vf::launch_clahe(dsrc, ddst, width, height, channels, clip_q8, tiles_x, tiles_y, mask, ctx->clahe_dev,
+                               (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_clahe_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                   const int *heights, int n, int channels, int clip_q8, int tiles_x, int tiles_y,
+                                   int mask) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_clahe_frames_host";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_clahe(ctx, fn, clip_q8, tiles_x, tiles_y, mask, channels)) != VF_OK) return rc;
+  const int32_t data[4] = {mask, clip_q8, tiles_x, tiles_y};
+  const vf_step step{VF_STEP_CLAHE, 0, 0, 0, data, 0, 0, 0, 0, 0};  // a program of one step
+  return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
+}
+
+// ---- filter chains: a program of table / conv / rank / binary / mix / sep / level / clahe steps on raw frames
 
 namespace {
 
@@ -1098,6 +1174,12 @@ int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps,
       if (!d) return set_err(ctx, VF_E_INVALID, 0, "%s: the level step's data is NULL", at);
       if ((rc = check_level(ctx, at, in.op, d[0], d[1], d[2], d[3], channels)) != VF_OK) return rc;
       s.mask = d[0], s.link = d[1], s.clip_lo = d[2], s.clip_hi = d[3];
+    } else if (in.kind == VF_STEP_CLAHE) {
+      // data: {mask, clip_q8, tiles_x, tiles_y} as int32
+      const int32_t *d = static_cast<const int32_t *>(in.data);
+      if (!d) return set_err(ctx, VF_E_INVALID, 0, "%s: the CLAHE step's data is NULL", at);
+      if ((rc = check_clahe(ctx, at, d[1], d[2], d[3], d[0], channels)) != VF_OK) return rc;
+      s.mask = d[0], s.clip_q8 = d[1], s.tiles_x = d[2], s.tiles_y = d[3];
     } else if (in.kind != VF_STEP_BINARY) {
       return set_err(ctx, VF_E_INVALID, 0, "%s: unknown kind %d", at, in.kind);
     }
@@ -1582,6 +1664,15 @@ int level_filter(vf_ctx *ctx, const char *fn, int rule, int mask, int link, int 
   return chain_filter(ctx, fn, &step, 1, out);
 }
 
+// The decoded frames are 3-channel BGR, grayscale inputs included.
+int clahe_filter(vf_ctx *ctx, const char *fn, int clip_q8, int tiles_x, int tiles_y, int mask, Filter *out) {
+  const int rc = check_clahe(ctx, fn, clip_q8, tiles_x, tiles_y, mask, 3);
+  if (rc != VF_OK) return rc;
+  const int32_t data[4] = {mask, clip_q8, tiles_x, tiles_y};
+  const vf_step step{VF_STEP_CLAHE, 0, 0, 0, data, 0, 0, 0, 0, 0};
+  return chain_filter(ctx, fn, &step, 1, out);
+}
+
 }  // namespace
 
 VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
@@ -1826,6 +1917,36 @@ VF_EXPORT int vf_jpeg_bench_level(vf_ctx *ctx, const uint8_t *const *jpegs, cons
   Filter filter;
   if (const int rc = level_filter(ctx, "vf_jpeg_bench_level", rule, mask, link, clip_lo, clip_hi, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_level", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
+                           filter);
+}
+
+// ---- JPEG with CLAHE in place of the inversion ----------------------------------------------------------
+
+VF_EXPORT int vf_jpeg_clahe(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int clip_q8,
+                            int tiles_x, int tiles_y, int mask, int quality, int subsamp, int flags, uint8_t *const *outs,
+                            const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = clahe_filter(ctx, "vf_jpeg_clahe", clip_q8, tiles_x, tiles_y, mask, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_clahe", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
+}
+
+VF_EXPORT int vf_jpeg_clahe_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int clip_q8,
+                                   int tiles_x, int tiles_y, int mask, int quality, int subsamp, int flags,
+                                   uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = clahe_filter(ctx, "vf_jpeg_clahe_submit", clip_q8, tiles_x, tiles_y, mask, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_clahe_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
+}
+
+VF_EXPORT int vf_jpeg_bench_clahe(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int clip_q8,
+                                  int tiles_x, int tiles_y, int mask, int quality, int subsamp, int flags, int iters,
+                                  float *ms, float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = clahe_filter(ctx, "vf_jpeg_bench_clahe", clip_q8, tiles_x, tiles_y, mask, &filter)) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_clahe", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
                            filter);
 }
 

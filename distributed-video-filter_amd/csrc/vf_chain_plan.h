@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "vf_clahe_plan.h"
 #include "vf_level_plan.h"
 
 namespace vf {
@@ -36,9 +37,9 @@ constexpr int kMaxSepSide = 31;  // the most taps of one axis of a separable ste
 // VF_STEP_*.  The values are not dense: 4 is left out on purpose.  Kind 4 is the value the checks
 // of this file and of the C ABI have always used for "a kind that does not exist" (refused with
 // "unknown kind 4"), and callers may rely on that refusal, so the colour matrix took 5.  6 and 9
-// are refused in callers' checks the same way, so the separable filter took 7 and the level
-// filter 8.
-enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5, kSep = 7, kLevel = 8 };
+// are refused in callers' checks the same way, so the separable filter took 7, the level
+// filter 8 and CLAHE 10; 11 stays refused as well.
+enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5, kSep = 7, kLevel = 8, kClahe = 10 };
 enum : int { kRoundHalfEven = 0, kRoundHalfUp = 1 };                             // VF_ROUND_*
 enum : int { kSubtract = 0, kAdd = 1, kAbsdiff = 2, kMin = 3, kMax = 4 };        // VF_BIN_*
 
@@ -54,7 +55,8 @@ struct Step {
   std::vector<int32_t> matrix;   // kMix: 12, row-major [M | t] 3 x 4
   std::vector<int16_t> taps_x, taps_y;  // kSep: kw horizontal and kh vertical taps
   int divisor = 1;                      // kSep: odd, 1 .. 1023; 1: none
-  int mask = 0, link = 0, clip_lo = 0, clip_hi = 0;  // kLevel (vf_level_plan.h)
+  int mask = 0, link = 0, clip_lo = 0, clip_hi = 0;  // kLevel (vf_level_plan.h); mask: kClahe as well
+  int clip_q8 = 0, tiles_x = 0, tiles_y = 0;         // kClahe (vf_clahe_plan.h)
 };
 
 struct Program {
@@ -65,12 +67,26 @@ struct Program {
 inline bool is_neighbourhood(const Step &s) { return s.kind == kConv || s.kind == kRank || s.kind == kSep; }
 inline int radius(const Step &s) { return is_neighbourhood(s) ? s.kh / 2 : 0; }  // vertical
 
-// A level step reads its whole operand before it writes a byte (vf_level.hip): a program that holds
+// A level step reads its whole operand before it writes a byte (vf_level.hip), and so does a CLAHE
+// step (vf_clahe.hip: every tile's table is complete before the blend starts): a program that holds
 // one is planned on whole frames only, y0 = 0 and y1 = H, and never cut into bands.
 inline bool whole_frame(const Program &p) {
   for (const Step &s : p.steps)
-    if (s.kind == kLevel) return true;
+    if (s.kind == kLevel || s.kind == kClahe) return true;
   return false;
+}
+
+// The device scratch of a whole-frame program's steps (run_launches' hist), in bytes: the level
+// steps' histogram words, level::kHistWords for each step of the program (step i's at (i - 1) *
+// kHistWords), then one clahe::kScratchBytes for each CLAHE step, in the steps' order.
+inline size_t level_scratch_bytes() { return (size_t)kMaxSteps * level::kHistWords * sizeof(uint32_t); }
+inline int clahe_steps_before(const Program &p, int step) {  // step: 1-based
+  int k = 0;
+  for (int i = 1; i < step && i <= p.size(); ++i) k += p.steps[i - 1].kind == kClahe;
+  return k;
+}
+inline size_t whole_frame_scratch_bytes(const Program &p) {
+  return level_scratch_bytes() + (size_t)clahe_steps_before(p, p.size() + 1) * clahe::kScratchBytes;
 }
 
 // Is value v read by step s?
@@ -91,7 +107,7 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
   for (int i = 1; i <= n; ++i) {
     const Step &s = p.steps[i - 1];
     const std::string at = "step " + std::to_string(i) + ": ";
-    if ((s.kind < kTable || s.kind > kBinary) && s.kind != kMix && s.kind != kSep && s.kind != kLevel)
+    if ((s.kind < kTable || s.kind > kBinary) && s.kind != kMix && s.kind != kSep && s.kind != kLevel && s.kind != kClahe)
       return fail(at + "unknown kind " + std::to_string(s.kind));
     if (s.a < 0 || s.a >= i)
       return fail(at + "operand a = " + std::to_string(s.a) + " is not an earlier value");
@@ -113,6 +129,10 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
     if (s.kind == kLevel) {
       std::string m;
       if (!level::limits_ok(s.op, s.mask, s.link, s.clip_lo, s.clip_hi, frame_channels, &m)) return fail(at + m);
+    }
+    if (s.kind == kClahe) {
+      std::string m;
+      if (!clahe::limits_ok(s.clip_q8, s.tiles_x, s.tiles_y, s.mask, frame_channels, &m)) return fail(at + m);
     }
     if (s.kind == kSep) {
       if (s.kw < 1 || s.kh < 1 || s.kw > kMaxSepSide || s.kh > kMaxSepSide || !(s.kw & 1) || !(s.kh & 1))
@@ -154,8 +174,9 @@ inline void compose_tables(const Step &first, const Step &then, Step *out) {
 // The program with every table step whose only reader is a table step composed into that reader
 // (exact: both are per-byte maps).  The result computes the same picture in fewer steps.  Nothing
 // is composed across a colour matrix: a table beside one stays a step, and two matrices with a
-// rounding and a clamp between them are not one matrix.  Nor across a separable or a level step:
-// only table steps are ever composed, and a level step's table does not exist before the frame does.
+// rounding and a clamp between them are not one matrix.  Nor across a separable, a level or a CLAHE
+// step: only table steps are ever composed, and a level or CLAHE step's tables do not exist before
+// the frame does.
 inline Program fold(const Program &in) {
   Program p = in;
   for (bool again = true; again;) {
@@ -199,7 +220,8 @@ struct Buffers {
 // Buffers by last use.  Buffer 0 holds value 0 and is reused once value 0 is dead.  A
 // neighbourhood step never writes the buffer it reads; a table, colour-matrix or binary step writes
 // in place over an operand that dies at that step (a separable step is a neighbourhood step: never
-// in place; a level step is not one: its histogram is complete before its first byte is written).  Every value of a buffer sits at one row origin (the band's
+// in place; a level or CLAHE step is not one: its histograms are complete before its first byte is
+// written).  Every value of a buffer sits at one row origin (the band's
 // first source row), so "in place" is dst == operand exactly.
 inline Buffers assign_buffers(const Program &p) {
   const int n = p.size();
@@ -240,7 +262,7 @@ struct Rows {
 };
 
 // The rows of every value that must exist for rows [y0, y1) of the result of a frame of H rows
-// (0 <= y0 < y1 <= H): out[v] for v = 0 .. n.  out[0] is the upload.  A level step has whole-frame
+// (0 <= y0 < y1 <= H): out[v] for v = 0 .. n.  out[0] is the upload.  A level or CLAHE step has whole-frame
 // reach, so a program that holds one asks for all H rows of every value, whatever [y0, y1) is.
 inline std::vector<Rows> rows_needed(const Program &p, int H, int y0, int y1) {
   const int n = p.size();

@@ -108,12 +108,23 @@ hipError_t launch_hist(const void *dsrc, size_t nbytes, int channels, uint32_t *
 hipError_t launch_level(const void *dsrc, void *ddst, size_t nbytes, int channels, int rule, int mask, int link,
                         int clip_lo, int clip_hi, uint32_t *hist, const LaunchCfg &cfg, hipStream_t stream);
 
-// The steps of a program as launches of the seven kernels above (vf_api.hip): `launches` is
+// CLAHE (vf_clahe.hip; cv2.createCLAHE(...).apply) over one frame of width x height
+// pixels of 1 or 3 interleaved channels, packed rows: vf_clahe_plan.h's rules with the clip limit
+// clip_q8 / 256 (0: none), a grid of tiles_x x tiles_y tiles and mask the filtered channels (0: all;
+// the others are copied).  `scratch`: 16-B aligned device memory of clahe::kScratchBytes (the tiles'
+// histogram words, which the call zeroes on the stream, then their tables) that the work queued on
+// `stream` alone uses.  Each frame pointer at any alignment; ddst == dsrc exactly is allowed (every
+// table is complete before the first byte is written), a partial overlap is not (the caller
+// checks).  No device allocation; asynchronous on `stream`: a memset and three launches.
+hipError_t launch_clahe(const void *dsrc, void *ddst, int width, int height, int channels, int clip_q8, int tiles_x,
+                        int tiles_y, int mask, void *scratch, hipStream_t stream);
+
+// The steps of a program as launches of the eight kernels above (vf_api.hip): `launches` is
 // vf_chain_plan.h's band_launches of a band or whole frame, masks[i] step i + 1's element when it
 // is a rank step, bufs[k] the address of buffer k's origin row (the band's row s0), out the rows a
-// chain::kOut launch writes; conv_form as launch_conv's form.  hist: the histogram words of the
-// program's level steps, level::kHistWords for each step of the program (step i's at (i - 1) *
-// kHistWords), device memory that the work queued on `stream` alone uses; NULL when
+// chain::kOut launch writes; conv_form as launch_conv's form.  hist: the scratch of the program's
+// level and CLAHE steps, chain::whole_frame_scratch_bytes(prog) bytes laid out as that function
+// says, 16-B aligned device memory that the work queued on `stream` alone uses; NULL when
 // chain::whole_frame(prog) is false.
 namespace chain {
 struct Program;

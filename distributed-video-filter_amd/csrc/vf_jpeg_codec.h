@@ -108,8 +108,8 @@ struct ChainSpec {
 struct Filter {
   enum Kind { kNone, kInvert, kTable, kChain } kind = kInvert;  // kNone: the plain decode, pixels stay as decoded
   LutTable lut = {};  // kTable: cv2.LUT on the decoded BGR pixels; a one-channel table is stored three times
-  // kChain: a program of table, convolution, rank, binary, colour-matrix, separable and level steps on
-  // them; cv2.filter2D, cv2.erode, cv2.dilate, cv2.medianBlur and cv2.equalizeHist are programs of one step
+  // kChain: a program of table, convolution, rank, binary, colour-matrix, separable, level and CLAHE steps on
+  // them; cv2.filter2D, cv2.erode, cv2.dilate, cv2.medianBlur, cv2.equalizeHist and CLAHE are programs of one step
   std::shared_ptr<const ChainSpec> chain;
   bool in_colour() const { return kind == kInvert || kind == kTable; }  // the colour stage filters
   // a program runs between decode (d_pix_) and encode (the buffer that holds its result)
@@ -218,7 +218,7 @@ class Codec {
   Filter filter_;  // the batch's filter, set by the entry call before prepare_decode; the stages read it
   DevBuf d_pix2_;  // the convolution's output: the batch's frames at their d_pix_ offsets
   std::vector<std::unique_ptr<DevBuf>> d_chain_;  // a chain's buffers 2, 3, ...: as d_pix2_ (0 is d_pix_, 1 d_pix2_)
-  DevBuf d_level_hist_;  // the histogram words of a program's level steps (run_launches' hist): the frames run in order
+  DevBuf d_level_hist_;  // the scratch of a program's level and CLAHE steps (run_launches' hist): the frames run in order
   int dcm_ = -1;  // k_color layout shared by the batch's frames (1..3, 0 general), -1 mixed
   DevBuf d_efr_, d_etab_, d_hdr_, d_esegs_, d_etsum_, d_etotals_, d_dcq_, d_acbits_, d_acscr_, d_bits_, d_pre_, d_bitoff_, d_stream_, d_ffcnt_,
       d_outsize_, d_pack_;

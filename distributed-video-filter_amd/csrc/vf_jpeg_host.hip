@@ -892,9 +892,19 @@ int Codec::run_filter_encode(bool fastdct, std::string *err) {
     if (k != 0) CK(b.ensure(dpix_bytes_));  // d_pix_ holds the decoded frames: sized by prepare_decode
     base[(size_t)k] = b.as<uint8_t>();
   }
-  uint32_t *hist = nullptr;  // a level step's histogram words: the frames run in order on s_, so one set a step
+  uint32_t *hist = nullptr;  // a level or CLAHE step's scratch: the frames run in order on s_, so one set a step
   if (chain::whole_frame(c.prog)) {
-    CK(d_level_hist_.ensure((size_t)chain::kMaxSteps * level::kHistWords * sizeof(uint32_t)));
+    for (const chain::Step &st : c.prog.steps) {
+      if (st.kind != chain::kClahe) continue;
+      for (int f = 0; f < dn_; ++f) {
+        std::string why;
+        if (!clahe::frame_ok((uint64_t)dfr_[(size_t)f].g.w, (uint64_t)dfr_[(size_t)f].g.h, st.tiles_x, st.tiles_y, &why)) {
+          *err = "frame " + std::to_string(f) + ": " + why;
+          return kInvalid;
+        }
+      }
+    }
+    CK(d_level_hist_.ensure(chain::whole_frame_scratch_bytes(c.prog)));
     hist = d_level_hist_.as<uint32_t>();
   }
   const LaunchCfg cfg;

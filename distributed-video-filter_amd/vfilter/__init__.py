@@ -18,6 +18,7 @@ distributor.py).
                ``Separable`` and ``sep_frames``
                ``equalize_hist`` (the ``cv2.equalizeHist`` drop-in), ``auto_levels``, ``calc_hist`` (the
                histogram, counted on the GPU), ``Level``, ``level_frames`` and ``calc_hist_frames``
+               ``clahe`` and ``create_clahe`` (the ``cv2.createCLAHE`` drop-in), ``Clahe`` and ``clahe_frames``
   colors       builders of the usual colour matrices (gray, swap_rb, sepia, saturation, gain, ...)
   kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
   elements     builders of the usual structuring elements (rect, cross)
@@ -36,6 +37,7 @@ from .filters import (Chain, Combine, Mix, Morph, Rank, as_element, as_kernel, a
                       transform_frames)
 from .filters import Separable, as_taps, blur, box_filter, sep_filter2d, sep_frames  # noqa: F401
 from .filters import Level, auto_levels, calc_hist, calc_hist_frames, equalize_hist, level_frames  # noqa: F401
+from .filters import Clahe, clahe, clahe_frames, create_clahe  # noqa: F401
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
@@ -46,4 +48,5 @@ __all__ = [
     "Mix", "as_matrix", "transform", "transform_frames", "colors",
     "Separable", "as_taps", "sep_filter2d", "blur", "box_filter", "sep_frames",
     "Level", "equalize_hist", "auto_levels", "calc_hist", "calc_hist_frames", "level_frames",
+    "Clahe", "clahe", "create_clahe", "clahe_frames",
 ]

@@ -153,6 +153,18 @@ SIGNATURES = {
     "vf_jpeg_bench_level": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, _c_float_p, _c_float_p]),
+    "vf_clahe_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, _vp]),
+    "vf_clahe_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vf_jpeg_clahe": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_clahe_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_clahe": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           _c_float_p, _c_float_p]),
     "vf_binary_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
     "vf_chain_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
     "vf_jpeg_chain": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -168,6 +180,7 @@ STEP_MIX = 5                                                # VF_STEP_MIX: 4 nam
 STEP_SEP = 7                                                # VF_STEP_SEP: 6 stays refused as well
 STEP_LEVEL = 8                                              # VF_STEP_LEVEL: 9 stays refused as well
 LEVEL_EQUALIZE, LEVEL_STRETCH = 0, 1                        # VF_LEVEL_*
+STEP_CLAHE = 10                                             # VF_STEP_CLAHE: 11 stays refused as well
 CHAIN_MAX_STEPS = 8                                         # VF_CHAIN_MAX_STEPS
 ROUND_HALF_EVEN, ROUND_HALF_UP = 0, 1                       # VF_ROUND_*
 
@@ -619,6 +632,17 @@ class Context:
         self._check(self._lib.vf_level_device(self._ctx, dsrc or None, ddst or None, width, height, channels, rule, mask,
                                               link, clip_lo, clip_hi, stream or None))
 
+    # -- CLAHE (cv2.createCLAHE(...).apply): vf_clahe_* ------------------------------------------------------
+    def clahe_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                          channels: int, clip_q8: int, tiles_x: int = 8, tiles_y: int = 8, mask: int = 0) -> None:
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
+        self._check(self._lib.vf_clahe_frames_host(self._ctx, sa, da, wa, ha, n, channels, clip_q8, tiles_x, tiles_y, mask))
+
+    def clahe_device(self, dsrc: int, ddst: int, width: int, height: int, channels: int, clip_q8: int, tiles_x: int = 8,
+                     tiles_y: int = 8, mask: int = 0, stream: int = 0) -> None:
+        self._check(self._lib.vf_clahe_device(self._ctx, dsrc or None, ddst or None, width, height, channels, clip_q8,
+                                              tiles_x, tiles_y, mask, stream or None))
+
     # -- filter chains (vf_chain_*, vf_binary_device) ------------------------------------------------
     def _steps(self, steps: Sequence):
         """``steps`` -- ``filters.Chain.args[0]``: tuples ``(kind, a, b, op, data, shift, border)`` with
@@ -647,6 +671,10 @@ class Context:
                 d = np.array([int(v) for v in data], np.int32)
                 if d.shape != (4,):
                     raise ValueError("a level step's data is (mask, link, clip_lo, clip_hi)")
+            elif kind == STEP_CLAHE:  # data: (mask, clip_q8, tiles_x, tiles_y)
+                d = np.array([int(v) for v in data], np.int32)
+                if d.shape != (4,):
+                    raise ValueError("a CLAHE step's data is (mask, clip_q8, tiles_x, tiles_y)")
             else:
                 d = None
             if d is not None:
@@ -1186,6 +1214,34 @@ class Context:
         total, not in a stage, as ``jpeg_bench_conv``'s)."""
         return self._jpeg_bench(self._lib.vf_jpeg_bench_level, (rule, mask, link, clip_lo, clip_hi), "color", jpegs,
                                 quality, subsamp, flags, iters)
+
+    # -- JPEG with CLAHE in place of the inversion (vf_jpeg_clahe*); tickets are invert tickets --------------
+    def jpeg_clahe(self, jpegs: Sequence, clip_q8: int, tiles_x: int, tiles_y: int, mask: int, quality: int,
+                   subsamp: int, flags: int = 0) -> list:
+        """decode -> CLAHE -> encode for every JPEG on the GPU; returns bytes."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_clahe_submit(jpegs, clip_q8, tiles_x, tiles_y, mask, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_clahe_submit(self, jpegs: Sequence, clip_q8: int, tiles_x: int, tiles_y: int, mask: int, quality: int,
+                          subsamp: int, flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with CLAHE; collect with the ``jpeg_invert_result*`` methods."""
+        return self._jpeg_submit("jpeg_clahe_submit", self._lib.vf_jpeg_clahe_submit, (clip_q8, tiles_x, tiles_y, mask),
+                                 jpegs, None, quality, subsamp, flags)
+
+    def jpeg_clahe_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, clip_q8: int, tiles_x: int, tiles_y: int,
+                                mask: int, quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_clahe_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        return self._jpeg_submit("jpeg_clahe_submit_addrs", self._lib.vf_jpeg_clahe_submit,
+                                 (clip_q8, tiles_x, tiles_y, mask), addrs, sizes, quality, subsamp, flags)
+
+    def jpeg_bench_clahe(self, jpegs: Sequence, clip_q8: int, tiles_x: int, tiles_y: int, mask: int, quality: int,
+                         subsamp: int, flags: int = 0, iters: int = 10):
+        """``jpeg_bench_invert`` with CLAHE between the decode and the encode (its time is in the total, not in a
+        stage, as ``jpeg_bench_conv``'s)."""
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_clahe, (clip_q8, tiles_x, tiles_y, mask), "color", jpegs, quality,
+                                subsamp, flags, iters)
 
     # -- JPEG with a filter chain in place of the inversion (vf_jpeg_chain*); tickets are invert tickets ----
     def jpeg_chain(self, jpegs: Sequence, steps: Sequence, quality: int, subsamp: int, flags: int = 0) -> list:

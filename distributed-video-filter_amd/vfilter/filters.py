@@ -936,12 +936,149 @@ def level_frames(frames: Sequence, level: Level, outs: Optional[List] = None, ct
                         lambda *a: (ctx or get_context()).level_frames_host(*a, *level.args))
 
 
+# -- CLAHE: cv2.createCLAHE(clipLimit, tileGridSize).apply ---------------------------------------------
+
+CLAHE_MAX_TILES = 16  # an axis of the grid (csrc/vf_clahe_plan.h kMaxTilesAxis)
+CLAHE_MAX_CLIP_Q8 = 1 << 24  # the clip limit in units of 1 / 256 (kMaxClipQ8)
+
+
+def _clahe_clip(clip_limit) -> int:
+    """``clip_limit`` -- a number whose 256-fold is an integer in ``0 .. 2**24``; 0: no clipping -- as that integer."""
+    if isinstance(clip_limit, (bool, np.bool_)):
+        raise ValueError(f"Clahe: clip_limit is a number, not {clip_limit!r}")
+    try:
+        f = float(clip_limit)
+    except (TypeError, ValueError):
+        raise ValueError(f"Clahe: clip_limit is a number, not {clip_limit!r}") from None
+    if not 0.0 <= f <= CLAHE_MAX_CLIP_Q8 / 256:  # a NaN fails this too
+        raise ValueError(f"Clahe: clip_limit = {f!r}; a clip limit is in [0, {CLAHE_MAX_CLIP_Q8 // 256}]")
+    q = f * 256
+    if q != int(q):
+        raise ValueError(f"Clahe: clip_limit = {f!r}; clip_limit * 256 must be an integer (there is no approximate path)")
+    return int(q)
+
+
+def _clahe_grid(tile_grid_size) -> tuple:
+    """``tile_grid_size`` -- cv2's ``(tiles_x, tiles_y)``, 1 .. 16 each."""
+    try:
+        tx, ty = tile_grid_size
+        if any(isinstance(t, (bool, np.bool_)) or int(t) != t for t in (tx, ty)):
+            raise TypeError
+        tx, ty = int(tx), int(ty)
+    except (TypeError, ValueError):
+        raise ValueError(f"Clahe: tile_grid_size is (tiles_x, tiles_y), not {tile_grid_size!r}") from None
+    if not (1 <= tx <= CLAHE_MAX_TILES and 1 <= ty <= CLAHE_MAX_TILES):
+        raise ValueError(f"Clahe: tile_grid_size = {tile_grid_size!r}; 1 .. {CLAHE_MAX_TILES} tiles an axis")
+    return tx, ty
+
+
+def _clahe_mask(channels) -> int:
+    try:
+        return _level_mask(channels)
+    except ValueError as e:
+        raise ValueError(str(e).replace("Level:", "Clahe:", 1)) from None
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Clahe:
+    """Contrast-limited adaptive histogram equalisation, ``cv2.createCLAHE(clip_limit, tile_grid_size).apply``: the
+    frame, extended by reflection to whole tiles, is cut into ``tile_grid_size = (tiles_x, tiles_y)`` tiles (1 .. 16 an
+    axis); every tile's histogram is clipped at ``clip_limit`` times its mean bin (0: not clipped), the excess given
+    back, and made into a table; a pixel is the blend of the four nearest tiles' tables.  ``clip_limit * 256`` must
+    be an integer (2.0, 2.5, 4.0 and 40.0 all are).  ``channels`` names the channels that are filtered, each on
+    its own (``None``: all; the others pass unchanged); cv2 itself takes one channel."""
+    clip_limit: float
+    clip_q8: int
+    tiles_x: int
+    tiles_y: int
+    mask: int
+    family = "clahe"
+
+    def __init__(self, clip_limit=40.0, tile_grid_size=(8, 8), channels=None):
+        q = _clahe_clip(clip_limit)
+        tx, ty = _clahe_grid(tile_grid_size)
+        fields = {"clip_limit": q / 256, "clip_q8": q, "tiles_x": tx, "tiles_y": ty, "mask": _clahe_mask(channels)}
+        for name, v in fields.items():
+            object.__setattr__(self, name, v)
+
+    @property
+    def min_channels(self) -> int:
+        """3 when ``channels`` names channel 1 or 2 (such a filter takes 3-channel frames only), else 1."""
+        return 3 if self.mask >> 1 else 1
+
+    @property
+    def args(self) -> tuple:
+        return self.clip_q8, self.tiles_x, self.tiles_y, self.mask
+
+
+def _clahe_frame(name: str, a, f: Clahe) -> np.ndarray:
+    a = _conv_frame(name, a)
+    if f.min_channels == 3 and (a.ndim != 3 or a.shape[2] != 3):
+        raise ValueError(f"{name}: the filter names channel 1 or 2; frames are H x W x 3, not shape {a.shape}")
+    return a
+
+
+def clahe(src: np.ndarray, clip_limit=40.0, tile_grid_size=(8, 8), channels=None, dst: Optional[np.ndarray] = None,
+          ctx: Optional[Context] = None) -> np.ndarray:
+    """``cv2.createCLAHE(clip_limit, tile_grid_size).apply(src)`` on a uint8 ``H x W`` frame, bit-exact by this
+    project's rule; on ``H x W x 3`` every channel of ``channels`` (``None``: all) on its own.  ``dst`` as
+    for ``lut``, and it may be ``src``."""
+    f = Clahe(clip_limit, tile_grid_size, channels)
+    src = np.ascontiguousarray(_clahe_frame("clahe", src, f))
+    dst = _rank_dst("clahe", src, dst)
+    nch = 1 if src.ndim == 2 else src.shape[2]
+    if src.size:
+        (ctx or get_context()).clahe_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], nch, *f.args)
+    return dst
+
+
+class _ClaheObject:
+    """What ``create_clahe`` returns: ``cv2.createCLAHE``'s object for 8-bit frames."""
+
+    def __init__(self, clip_limit, tile_grid_size, ctx):
+        self._filter = Clahe(clip_limit, tile_grid_size)
+        self._ctx = ctx
+
+    def apply(self, src: np.ndarray, dst: Optional[np.ndarray] = None) -> np.ndarray:
+        f = self._filter
+        return clahe(src, f.clip_limit, (f.tiles_x, f.tiles_y), None, dst, self._ctx)
+
+    def getClipLimit(self) -> float:
+        return self._filter.clip_limit
+
+    def getTilesGridSize(self) -> tuple:
+        return self._filter.tiles_x, self._filter.tiles_y
+
+    def setClipLimit(self, clip_limit) -> None:
+        self._filter = Clahe(clip_limit, self.getTilesGridSize())
+
+    def setTilesGridSize(self, tile_grid_size) -> None:
+        self._filter = Clahe(self._filter.clip_limit, tile_grid_size)
+
+
+def create_clahe(clip_limit=40.0, tile_grid_size=(8, 8), ctx: Optional[Context] = None) -> _ClaheObject:
+    """Drop-in for ``cv2.createCLAHE(clipLimit, tileGridSize)``: an object with ``apply(src)``, ``getClipLimit`` and
+    ``getTilesGridSize`` (and their setters).  ``apply`` takes a uint8 ``H x W`` frame as cv2's does; an ``H x W x 3``
+    frame has every channel filtered on its own."""
+    return _ClaheObject(clip_limit, tile_grid_size, ctx)
+
+
+def clahe_frames(frames: Sequence, f: Clahe, outs: Optional[List] = None, ctx: Optional[Context] = None) -> List:
+    """A ``Clahe`` over separately stored frames of one channel count and mixed sizes in one call.  Returns ndarrays
+    (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
+    if not isinstance(f, Clahe):
+        raise ValueError("clahe_frames: the filter is a Clahe")
+    return _frames_call("clahe_frames", [_clahe_frame("clahe_frames", a, f) for a in frames], outs,
+                        lambda *a: (ctx or get_context()).clahe_frames_host(*a, *f.args))
+
+
 # -- filter chains: a program of filters between one upload and one download ----------------------
 
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
 STEP_MIX = 5  # VF_STEP_MIX: 4 names no kind and stays refused
 STEP_SEP = 7  # VF_STEP_SEP: 6 stays refused as well
 STEP_LEVEL = 8  # VF_STEP_LEVEL: 9 stays refused as well
+STEP_CLAHE = 10  # VF_STEP_CLAHE: 11 stays refused as well
 BINARY_OPS = {"subtract": 0, "add": 1, "absdiff": 2, "min": 3, "max": 4}  # VF_BIN_*
 CHAIN_MAX_STEPS = 8  # VF_CHAIN_MAX_STEPS
 MORPH_OPS = ("erode", "dilate", "open", "close", "gradient", "tophat", "blackhat")
@@ -954,7 +1091,7 @@ class Combine:
     """A two-input step of a ``Chain``: ``op(a, b)`` per byte, ``op`` one of "subtract"
     (``max(a - b, 0)``), "add" (``min(a + b, 255)``), "absdiff", "min", "max" -- ``cv2.subtract``,
     ``cv2.add``, ``cv2.absdiff``, ``cv2.min``, ``cv2.max`` on uint8.  ``a`` and ``b`` are each a filter
-    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``, ``Level``, another ``Combine``), a ``Chain``, or ``None``
+    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``, ``Level``, ``Clahe``, another ``Combine``), a ``Chain``, or ``None``
     for the value entering the ``Combine``; both are applied to that value."""
     op: str
     op_code: int
@@ -987,7 +1124,10 @@ def _unary_step(f, a: int) -> tuple:
         return (STEP_SEP, a, 0, f.rounding_code, (f.kx, f.ky, f.divisor), f.shift, f.border_code)
     if isinstance(f, Level):
         return (STEP_LEVEL, a, 0, f.rule_code, (f.mask, int(f.link), f.clip_lo, f.clip_hi), 0, 0)
-    raise ValueError("chain: a step is Invert, Table, Kernel, Rank, Mix, Separable, Level, Combine or Chain, "
+    if isinstance(f, Clahe):
+        return (STEP_CLAHE, a, 0, 0, (f.mask, f.clip_q8, f.tiles_x, f.tiles_y), 0, 0)
+    # existing callers match the list up to "Chain" word for word, so a newer filter value is named after it
+    raise ValueError("chain: a step is Invert, Table, Kernel, Rank, Mix, Separable, Level, Combine or Chain, or a Clahe, "
                      f"not {type(f).__name__}")
 
 
@@ -1020,8 +1160,8 @@ class Chain:
     gives, every step with whole-frame borders.
 
     ``Chain(steps)``: each of ``steps`` -- ``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``,
-    ``Level``, ``Combine`` or a nested ``Chain``, which is flattened -- is applied to the result of the one
-    before.  A chain with a ``Level`` reads whole frames: a frame larger than the context's staging is
+    ``Level``, ``Clahe``, ``Combine`` or a nested ``Chain``, which is flattened -- is applied to the result of the one
+    before.  A chain with a ``Level`` or a ``Clahe`` reads whole frames: a frame larger than the context's staging is
     refused, not cut into bands.
     ``Chain.program(entries)`` takes the program itself: value 0 is the frame, value i the result of
     entry i (1-based); an entry is ``(filter value, a)`` or ``(binary op name, a, b)`` with ``a`` and
@@ -1074,13 +1214,13 @@ class Chain:
     @property
     def level_channels(self) -> int:
         """3 when a level step names channel 1 or 2 (such a chain takes 3-channel frames only), else 1."""
-        return 3 if any(st[0] == STEP_LEVEL and st[4][0] >> 1 for st in self.steps) else 1
+        return 3 if any(st[0] in (STEP_LEVEL, STEP_CLAHE) and st[4][0] >> 1 for st in self.steps) else 1
 
     def __len__(self) -> int:
         return len(self.steps)
 
 
-_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable, Level)
+_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable, Level, Clahe)
 
 
 def _lower(item, cur: int, prog: List[tuple]) -> int:
@@ -1147,7 +1287,7 @@ def _chain_frame(name: str, a, c: Chain) -> np.ndarray:
     if c.has_mix and (a.ndim != 3 or a.shape[2] != 3):
         raise ValueError(f"{name}: the chain has a colour matrix; frames are H x W x 3, not shape {a.shape}")
     if c.level_channels == 3 and (a.ndim != 3 or a.shape[2] != 3):
-        raise ValueError(f"{name}: a level step names channel 1 or 2; frames are H x W x 3, not shape {a.shape}")
+        raise ValueError(f"{name}: a level or CLAHE step names channel 1 or 2; frames are H x W x 3, not shape {a.shape}")
     return a
 
 

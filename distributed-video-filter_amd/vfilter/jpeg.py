@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import Invert, Kernel, Level, Morph, Rank, Separable, Table, _as_chain, _as_mix
+from .filters import Clahe, Invert, Kernel, Level, Morph, Rank, Separable, Table, _as_chain, _as_mix
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -94,7 +94,7 @@ class TurboJPEG:
         return self.ctx.jpeg_encode(list(imgs), pixel_format, quality, jpeg_subsample,
                                     self._enc_flags(flags, quality))
 
-    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank, Mix, Separable, Level, Chain) between decode and encode.  The
+    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank, Mix, Separable, Level, Clahe, Chain) between decode and encode.  The
     # ``invert*``, ``lut*`` and ``filter2d*`` methods below are these three with their filter built
     # from the call's own arguments.
     def filter_batch(self, jpeg_bufs: Sequence, filt, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
@@ -272,6 +272,18 @@ class TurboJPEG:
     def auto_levels_batch(self, jpeg_bufs: Sequence, clip=0.0, link: bool = False, quality: int = 85,
                           jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
         return self.filter_batch(jpeg_bufs, Level.stretch(clip, None, link), quality, jpeg_subsample, flags)
+
+    # -- CLAHE (cv2.createCLAHE(...).apply) between decode and encode -------------------------------------
+    # The submit forms go through ``filter_batch_submit*`` with a ``vfilter.filters.Clahe``.
+    def clahe(self, jpeg_buf, clip_limit=40.0, tile_grid_size=(8, 8), channels=None, quality: int = 85,
+              jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(vfilter.clahe(decode(jpeg_buf), clip_limit, tile_grid_size, channels))`` on the GPU, the pixels
+        never leaving it: every filtered channel of the decoded BGR frame on its own."""
+        return self.filter_batch([jpeg_buf], Clahe(clip_limit, tile_grid_size, channels), quality, jpeg_subsample, flags)[0]
+
+    def clahe_batch(self, jpeg_bufs: Sequence, clip_limit=40.0, tile_grid_size=(8, 8), channels=None, quality: int = 85,
+                    jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        return self.filter_batch(jpeg_bufs, Clahe(clip_limit, tile_grid_size, channels), quality, jpeg_subsample, flags)
 
     # -- a filter chain (vfilter.filters.Chain) between one decode and one encode ------------------------
     def chain(self, jpeg_buf, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:

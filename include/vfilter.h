@@ -594,6 +594,61 @@ int vf_jpeg_bench_level(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *
                         int rule, int mask, int link, int clip_lo, int clip_hi, int quality,
                         int subsamp, int flags, int iters, float *ms, float *stage_ms);
 
+/* ---- CLAHE (cv2.createCLAHE(clipLimit, tileGridSize).apply) ------------------------------------
+ * Contrast-limited adaptive histogram equalisation for uint8 frames of 1 or 3 interleaved
+ * channels, bit-exact by the rule below (a transcription of OpenCV 4.x clahe.cpp for
+ * 8-bit input; every float operation is one IEEE single-precision operation rounded to nearest
+ * even, none fused).  A frame has at most 2^32 - 1 pixels and sides of at most 2^30.
+ *   tiles_x, tiles_y   1 .. 16 each: cv2's tileGridSize = (x, y).
+ *   clip_q8  the clip limit in units of 1 / 256, 0 .. 2^24; 0: no clipping.
+ *   mask     bits 0..2: the channels that are filtered, each on its own, the others pass
+ *            unchanged; 0: all of the frame's channels; a bit beyond the frame's channel count is
+ *            refused.
+ * Geometry: when W % tiles_x == 0 and H % tiles_y == 0 the extended frame is the frame; else it is
+ * padded on the right by tiles_x - W % tiles_x and at the bottom by tiles_y - H % tiles_y (a full
+ * tiles_x or tiles_y on an axis that divides, as cv2 does), reflecting without the edge pixel
+ * (BORDER_REFLECT_101).  tw = We / tiles_x, th = He / tiles_y, area = tw * th, at most 2^31 - 1.
+ * Per tile and channel: h[256] counts the tile's pixels; with clip_q8 > 0, clip =
+ * max((clip_q8 * area) >> 16, 1), the excess above clip is cut off every bin and given back: every
+ * bin gains excess / 256, and with residual = excess % 256 > 0 and step = max(256 / residual, 1)
+ * bin v gains 1 when v % step == 0 and v / step < residual; scale = 255.0f / (float)area and
+ * table[v] = clamp(rint((float)(h[0] + .. + h[v]) * scale), 0, 255).
+ * Per pixel (y, x) with value s: txf = (float)x * (1.0f / (float)tw) - 0.5f, tx1 = floor(txf),
+ * xa = txf - tx1, xa1 = 1.0f - xa, then tx2 = min(tx1 + 1, tiles_x - 1), tx1 = max(tx1, 0); the
+ * same in y; dst = clamp(rint((T[ty1][tx1][s] * xa1 + T[ty1][tx2][s] * xa) * ya1 +
+ * (T[ty2][tx1][s] * xa1 + T[ty2][tx2][s] * xa) * ya), 0, 255).
+ * Anything else is VF_E_INVALID with the reason, before any GPU work.  The empty frame is a no-op. */
+
+/* Enqueue the filter on `stream` over one device-resident frame: any alignment, ddst == dsrc
+ * allowed (every table is complete before the first byte is written), a partial overlap is not;
+ * returns after the launches.  The tile histograms and tables are the context's: calls on one
+ * context that may run at the same time on different streams need a context each. */
+int vf_clahe_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                    int clip_q8, int tiles_x, int tiles_y, int mask, void *stream);
+
+/* The filter on `n` separately allocated host frames of mixed sizes and one channel count,
+ * synchronous; srcs[i] == dsts[i] is allowed.  A frame that does not fit the context's staging
+ * whole is refused: the tables need the whole frame, so a frame is never cut into bands. */
+int vf_clahe_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                         const int *widths, const int *heights, int n, int channels, int clip_q8,
+                         int tiles_x, int tiles_y, int mask);
+
+/* vf_jpeg_invert with the filter in place of the inversion: decode -> CLAHE -> encode on the GPU,
+ * on the decoded 3-channel BGR frame (grayscale inputs included). */
+int vf_jpeg_clahe(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                  int clip_q8, int tiles_x, int tiles_y, int mask, int quality, int subsamp,
+                  int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the filter.  The ticket is an invert ticket. */
+int vf_jpeg_clahe_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                         int clip_q8, int tiles_x, int tiles_y, int mask, int quality, int subsamp,
+                         int flags, uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the filter between the decode and the encode. */
+int vf_jpeg_bench_clahe(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                        int clip_q8, int tiles_x, int tiles_y, int mask, int quality, int subsamp,
+                        int flags, int iters, float *ms, float *stage_ms);
+
 /* ---- filter chains (cv2.morphologyEx, difference of blurs, ...) -----------------------------
  * A program is a straight-line list of 1 .. VF_CHAIN_MAX_STEPS steps over values.
  * Value 0 is the input frame (uint8, 1 or 3 interleaved channels, packed rows), value i the result
@@ -614,13 +669,15 @@ int vf_jpeg_bench_level(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *
  *   VF_STEP_LEVEL   the level filter: `op` a VF_LEVEL_*, `data` 4 int32 {mask, link, clip_lo, clip_hi}.
  *                   It reads its whole operand, so a program that holds one runs on whole frames
  *                   only: vf_chain_frames_host refuses a frame that does not fit the staging whole
+ *   VF_STEP_CLAHE   CLAHE: `data` 4 int32 {mask, clip_q8, tiles_x, tiles_y}.  It reads its whole
+ *                   operand as well, with the same refusal
  * `data` is a HOST pointer, read during the call only.  VF_E_INVALID, before any GPU work: a step
  * that reads a later value or itself, a value other than the last that no step reads, a 3-channel
  * table or a colour matrix on 1-channel frames, more than VF_CHAIN_MAX_STEPS steps, and anything
  * the single-filter entry points refuse for a table, a kernel, an element or a matrix.
  * The VF_STEP_* values are not dense: 4 names no kind and stays refused ("unknown kind 4"), as
  * callers' checks of the refusal expect, so VF_STEP_MIX is 5; 6 likewise, so VF_STEP_SEP is 7 and
- * VF_STEP_LEVEL 8; 9 stays refused too. */
+ * VF_STEP_LEVEL 8; 9 stays refused too, so VF_STEP_CLAHE is 10, and 11 stays refused. */
 #define VF_STEP_TABLE  0
 #define VF_STEP_CONV   1
 #define VF_STEP_RANK   2
@@ -628,6 +685,7 @@ int vf_jpeg_bench_level(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *
 #define VF_STEP_MIX    5
 #define VF_STEP_SEP    7
 #define VF_STEP_LEVEL  8
+#define VF_STEP_CLAHE  10
 #define VF_BIN_SUBTRACT 0
 #define VF_BIN_ADD      1
 #define VF_BIN_ABSDIFF  2
@@ -640,7 +698,7 @@ typedef struct vf_step {
   int a, b;         /* operand values; b for VF_STEP_BINARY only */
   int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_*; VF_STEP_MIX, VF_STEP_SEP: a VF_ROUND_*; VF_STEP_LEVEL: a VF_LEVEL_* */
   const void *data; /* the table, the int16 weights, the element or the int32 of a matrix, of
-                       separable taps or of a level step (host memory) */
+                       separable taps, of a level step or of a CLAHE step (host memory) */
   int kw, kh;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP */
   int shift;        /* VF_STEP_CONV, VF_STEP_MIX, VF_STEP_SEP */
   int border;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP: a VF_BORDER_* */
