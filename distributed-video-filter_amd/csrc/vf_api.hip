@@ -35,6 +35,7 @@
 #include "vf_sep_plan.h"
 #include "vf_level_plan.h"
 #include "vf_clahe_plan.h"
+#include "vf_warp_plan.h"
 #include "vf_jpeg_codec.h"
 #include "vf_lut_split.h"
 #include "vf_conv_bands.h"
@@ -592,6 +593,10 @@ hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const
                                  (size_t)chain::clahe_steps_before(prog, l.step) * clahe::kScratchBytes,
                              stream)
               : hipErrorInvalidValue;
+    else if (s.kind == chain::kWarp)  // whole frames only as well; never in place (chain::reads_elsewhere)
+      e = l.nrows == frame_h && a != dst
+              ? launch_warp(a, dst, w, frame_h, channels, s.warp.m, s.warp.mode, s.warp.interp, s.border, s.warp.value, stream)
+              : hipErrorInvalidValue;
     else
       e = hipErrorInvalidValue;  // no kernel for the kind: validate() lets none through
     if (e != hipSuccess) return e;
@@ -649,6 +654,10 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
       for (const vf::chain::Step &s : prog.steps)
         if (s.kind == vf::chain::kClahe &&
             !vf::clahe::frame_ok((uint64_t)widths[i], (uint64_t)heights[i], s.tiles_x, s.tiles_y, &why))
+          return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
+      for (const vf::chain::Step &s : prog.steps)
+        if (s.kind == vf::chain::kWarp &&
+            !vf::warp::frame_ok((uint64_t)widths[i], (uint64_t)heights[i], s.warp.mode, s.warp.m, &why))
           return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
       if (row * (size_t)heights[i] > cap)
         return set_err(ctx, VF_E_INVALID, 0,
@@ -1107,7 +1116,67 @@ VF_EXPORT int vf_clahe_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint
   return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
 }
 
-// ---- filter chains: a program of table / conv / rank / binary / mix / sep / level / clahe steps on raw frames
+// ---- the affine warp (cv2.warpAffine, cv2.flip) on raw frames ------------------------------------------
+
+namespace {
+
+// The filter arguments every vf_warp_* / vf_jpeg_warp* entry point and a VF_STEP_WARP step share
+// (vf_warp_plan.h has the limits).
+int check_warp(vf_ctx *ctx, const char *fn, const double *m, int mode, int interp, int border, const int *value,
+               int channels) {
+  std::string why;
+  if (!vf::warp::limits_ok(m, mode, interp, border, value, channels, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  return VF_OK;
+}
+
+// A VF_STEP_WARP step's data (include/vfilter.h): six float64, then {mode, interp, value B, G, R, 0}.
+struct WarpStepData {
+  double m[6];
+  int32_t i[6];
+};
+static_assert(sizeof(WarpStepData) == vf::warp::kStepBytes, "the step's data is packed");
+
+WarpStepData warp_step_data(const double *m, int mode, int interp, const int *value) {
+  WarpStepData d = {};
+  if (m && mode == vf::warp::kAffine) std::memcpy(d.m, m, sizeof d.m);
+  d.i[0] = mode, d.i[1] = interp, d.i[2] = value[0], d.i[3] = value[1], d.i[4] = value[2];
+  return d;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_warp_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels, const double *m,
+                             int mode, int interp, int border, const int *value, void *stream) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_warp_device";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_warp(ctx, fn, m, mode, interp, border, value, channels)) != VF_OK) return rc;
+  if ((rc = check_device_frame(ctx, fn, dsrc, ddst, width, height, channels)) != VF_OK) return rc < 0 ? rc : VF_OK;
+  std::string why;
+  if (!vf::warp::frame_ok((uint64_t)width, (uint64_t)height, mode, m, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  const uint8_t v[3] = {(uint8_t)value[0], (uint8_t)value[1], (uint8_t)value[2]};
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, vf::launch_warp(dsrc, ddst, width, height, channels, m, mode, interp, border, v, (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_warp_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                  const int *heights, int n, int channels, const double *m, int mode, int interp,
+                                  int border, const int *value) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_warp_frames_host";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_warp(ctx, fn, m, mode, interp, border, value, channels)) != VF_OK) return rc;
+  const WarpStepData data = warp_step_data(m, mode, interp, value);
+  const vf_step step{VF_STEP_WARP, 0, 0, 0, &data, 0, 0, 0, border, 0};  // a program of one step
+  return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
+}
+
+// ---- filter chains: a program of table / conv / rank / binary / mix / sep / level / clahe / warp steps on raw frames
 
 namespace {
 
@@ -1180,6 +1249,15 @@ int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps,
       if (!d) return set_err(ctx, VF_E_INVALID, 0, "%s: the CLAHE step's data is NULL", at);
       if ((rc = check_clahe(ctx, at, d[1], d[2], d[3], d[0], channels)) != VF_OK) return rc;
       s.mask = d[0], s.clip_q8 = d[1], s.tiles_x = d[2], s.tiles_y = d[3];
+    } else if (in.kind == VF_STEP_WARP) {
+      // data: six float64 (m), then {mode, interp, value B, G, R, 0} as int32; border: a VF_BORDER_*
+      if (!in.data) return set_err(ctx, VF_E_INVALID, 0, "%s: the warp step's data is NULL", at);
+      WarpStepData d;
+      std::memcpy(&d, in.data, sizeof d);  // host memory of any alignment
+      if ((rc = check_warp(ctx, at, d.m, d.i[0], d.i[1], in.border, d.i + 2, channels)) != VF_OK) return rc;
+      std::memcpy(s.warp.m, d.m, sizeof d.m);
+      s.warp.mode = d.i[0], s.warp.interp = d.i[1], s.border = in.border;
+      for (int c = 0; c < 3; ++c) s.warp.value[c] = (uint8_t)d.i[2 + c];
     } else if (in.kind != VF_STEP_BINARY) {
       return set_err(ctx, VF_E_INVALID, 0, "%s: unknown kind %d", at, in.kind);
     }
@@ -1673,6 +1751,16 @@ int clahe_filter(vf_ctx *ctx, const char *fn, int clip_q8, int tiles_x, int tile
   return chain_filter(ctx, fn, &step, 1, out);
 }
 
+// The decoded frames are 3-channel BGR, grayscale inputs included.
+int warp_filter(vf_ctx *ctx, const char *fn, const double *m, int mode, int interp, int border, const int *value,
+                Filter *out) {
+  const int rc = check_warp(ctx, fn, m, mode, interp, border, value, 3);
+  if (rc != VF_OK) return rc;
+  const WarpStepData data = warp_step_data(m, mode, interp, value);
+  const vf_step step{VF_STEP_WARP, 0, 0, 0, &data, 0, 0, 0, border, 0};
+  return chain_filter(ctx, fn, &step, 1, out);
+}
+
 }  // namespace
 
 VF_EXPORT int vf_jpeg_invert(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int quality,
@@ -1947,6 +2035,36 @@ VF_EXPORT int vf_jpeg_bench_clahe(vf_ctx *ctx, const uint8_t *const *jpegs, cons
   Filter filter;
   if (const int rc = clahe_filter(ctx, "vf_jpeg_bench_clahe", clip_q8, tiles_x, tiles_y, mask, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_clahe", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
+                           filter);
+}
+
+// ---- JPEG with the affine warp in place of the inversion ---------------------------------------------
+
+VF_EXPORT int vf_jpeg_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, const double *m,
+                           int mode, int interp, int border, const int *value, int quality, int subsamp, int flags,
+                           uint8_t *const *outs, const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = warp_filter(ctx, "vf_jpeg_warp", m, mode, interp, border, value, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_warp", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
+}
+
+VF_EXPORT int vf_jpeg_warp_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, const double *m,
+                                  int mode, int interp, int border, const int *value, int quality, int subsamp, int flags,
+                                  uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = warp_filter(ctx, "vf_jpeg_warp_submit", m, mode, interp, border, value, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_warp_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
+}
+
+VF_EXPORT int vf_jpeg_bench_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, const double *m,
+                                 int mode, int interp, int border, const int *value, int quality, int subsamp, int flags,
+                                 int iters, float *ms, float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = warp_filter(ctx, "vf_jpeg_bench_warp", m, mode, interp, border, value, &filter)) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_warp", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
                            filter);
 }
 

@@ -26,6 +26,7 @@
 
 #include "vf_clahe_plan.h"
 #include "vf_level_plan.h"
+#include "vf_warp_plan.h"
 
 namespace vf {
 namespace chain {
@@ -38,8 +39,8 @@ constexpr int kMaxSepSide = 31;  // the most taps of one axis of a separable ste
 // of this file and of the C ABI have always used for "a kind that does not exist" (refused with
 // "unknown kind 4"), and callers may rely on that refusal, so the colour matrix took 5.  6 and 9
 // are refused in callers' checks the same way, so the separable filter took 7, the level
-// filter 8 and CLAHE 10; 11 stays refused as well.
-enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5, kSep = 7, kLevel = 8, kClahe = 10 };
+// filter 8 and CLAHE 10; 11 stays refused as well, so the warp took 12, and 13 stays refused.
+enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5, kSep = 7, kLevel = 8, kClahe = 10, kWarp = 12 };
 enum : int { kRoundHalfEven = 0, kRoundHalfUp = 1 };                             // VF_ROUND_*
 enum : int { kSubtract = 0, kAdd = 1, kAbsdiff = 2, kMin = 3, kMax = 4 };        // VF_BIN_*
 
@@ -57,6 +58,7 @@ struct Step {
   int divisor = 1;                      // kSep: odd, 1 .. 1023; 1: none
   int mask = 0, link = 0, clip_lo = 0, clip_hi = 0;  // kLevel (vf_level_plan.h); mask: kClahe as well
   int clip_q8 = 0, tiles_x = 0, tiles_y = 0;         // kClahe (vf_clahe_plan.h)
+  warp::StepData warp = {};                          // kWarp (vf_warp_plan.h); border: kWarp as well
 };
 
 struct Program {
@@ -66,13 +68,17 @@ struct Program {
 
 inline bool is_neighbourhood(const Step &s) { return s.kind == kConv || s.kind == kRank || s.kind == kSep; }
 inline int radius(const Step &s) { return is_neighbourhood(s) ? s.kh / 2 : 0; }  // vertical
+// A step that reads its operand at other places than the one it writes, so never in place: the
+// neighbourhood steps, and a warp step (radius 0: its reach is the whole frame, see whole_frame).
+inline bool reads_elsewhere(const Step &s) { return is_neighbourhood(s) || s.kind == kWarp; }
 
 // A level step reads its whole operand before it writes a byte (vf_level.hip), and so does a CLAHE
 // step (vf_clahe.hip: every tile's table is complete before the blend starts): a program that holds
-// one is planned on whole frames only, y0 = 0 and y1 = H, and never cut into bands.
+// one is planned on whole frames only, y0 = 0 and y1 = H, and never cut into bands.  A warp step
+// (vf_warp.hip) reads anywhere in its operand, with the same consequence.
 inline bool whole_frame(const Program &p) {
   for (const Step &s : p.steps)
-    if (s.kind == kLevel || s.kind == kClahe) return true;
+    if (s.kind == kLevel || s.kind == kClahe || s.kind == kWarp) return true;
   return false;
 }
 
@@ -107,7 +113,8 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
   for (int i = 1; i <= n; ++i) {
     const Step &s = p.steps[i - 1];
     const std::string at = "step " + std::to_string(i) + ": ";
-    if ((s.kind < kTable || s.kind > kBinary) && s.kind != kMix && s.kind != kSep && s.kind != kLevel && s.kind != kClahe)
+    if ((s.kind < kTable || s.kind > kBinary) && s.kind != kMix && s.kind != kSep && s.kind != kLevel && s.kind != kClahe &&
+        s.kind != kWarp)
       return fail(at + "unknown kind " + std::to_string(s.kind));
     if (s.a < 0 || s.a >= i)
       return fail(at + "operand a = " + std::to_string(s.a) + " is not an earlier value");
@@ -133,6 +140,11 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
     if (s.kind == kClahe) {
       std::string m;
       if (!clahe::limits_ok(s.clip_q8, s.tiles_x, s.tiles_y, s.mask, frame_channels, &m)) return fail(at + m);
+    }
+    if (s.kind == kWarp) {
+      std::string m;
+      const int value[3] = {s.warp.value[0], s.warp.value[1], s.warp.value[2]};
+      if (!warp::limits_ok(s.warp.m, s.warp.mode, s.warp.interp, s.border, value, frame_channels, &m)) return fail(at + m);
     }
     if (s.kind == kSep) {
       if (s.kw < 1 || s.kh < 1 || s.kw > kMaxSepSide || s.kh > kMaxSepSide || !(s.kw & 1) || !(s.kh & 1))
@@ -176,7 +188,8 @@ inline void compose_tables(const Step &first, const Step &then, Step *out) {
 // is composed across a colour matrix: a table beside one stays a step, and two matrices with a
 // rounding and a clamp between them are not one matrix.  Nor across a separable, a level or a CLAHE
 // step: only table steps are ever composed, and a level or CLAHE step's tables do not exist before
-// the frame does.
+// the frame does.  Nor across a warp step: a table before one is not a table after one when the
+// constant border's colour enters the blend.
 inline Program fold(const Program &in) {
   Program p = in;
   for (bool again = true; again;) {
@@ -221,7 +234,8 @@ struct Buffers {
 // neighbourhood step never writes the buffer it reads; a table, colour-matrix or binary step writes
 // in place over an operand that dies at that step (a separable step is a neighbourhood step: never
 // in place; a level or CLAHE step is not one: its histograms are complete before its first byte is
-// written).  Every value of a buffer sits at one row origin (the band's
+// written; a warp step reads anywhere in its operand: never in place either, reads_elsewhere).  Every
+// value of a buffer sits at one row origin (the band's
 // first source row), so "in place" is dst == operand exactly.
 inline Buffers assign_buffers(const Program &p) {
   const int n = p.size();
@@ -237,7 +251,7 @@ inline Buffers assign_buffers(const Program &p) {
   for (int i = 1; i <= n; ++i) {
     const Step &s = p.steps[i - 1];
     int pick = -1;
-    if (!is_neighbourhood(s)) {  // in place over an operand that dies here
+    if (!reads_elsewhere(s)) {  // in place over an operand that dies here
       if (last[s.a] == i) pick = out.of[s.a];
       else if (s.kind == kBinary && last[s.b] == i) pick = out.of[s.b];
     }
@@ -262,7 +276,7 @@ struct Rows {
 };
 
 // The rows of every value that must exist for rows [y0, y1) of the result of a frame of H rows
-// (0 <= y0 < y1 <= H): out[v] for v = 0 .. n.  out[0] is the upload.  A level or CLAHE step has whole-frame
+// (0 <= y0 < y1 <= H): out[v] for v = 0 .. n.  out[0] is the upload.  A level, CLAHE or warp step has whole-frame
 // reach, so a program that holds one asks for all H rows of every value, whatever [y0, y1) is.
 inline std::vector<Rows> rows_needed(const Program &p, int H, int y0, int y1) {
   const int n = p.size();

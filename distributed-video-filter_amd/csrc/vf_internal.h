@@ -119,7 +119,17 @@ hipError_t launch_level(const void *dsrc, void *ddst, size_t nbytes, int channel
 hipError_t launch_clahe(const void *dsrc, void *ddst, int width, int height, int channels, int clip_q8, int tiles_x,
                         int tiles_y, int mask, void *scratch, hipStream_t stream);
 
-// The steps of a program as launches of the eight kernels above (vf_api.hip): `launches` is
+// The affine warp (vf_warp.hip; cv2.warpAffine and cv2.flip) over one frame of width x
+// height pixels of 1 or 3 interleaved channels, packed rows: vf_warp_plan.h's rules with the map
+// `m` from destination to source (six doubles; read when mode is 0, else the flip of `mode` is
+// resolved for this frame), interp 0 linear or 1 nearest, a VF_BORDER_* and the constant border's
+// bytes value[3].  Each frame pointer at any alignment; ddst must not overlap dsrc (the caller
+// checks: an output pixel reads anywhere).  No device memory of its own; asynchronous on `stream`:
+// one launch.
+hipError_t launch_warp(const void *dsrc, void *ddst, int width, int height, int channels, const double *m, int mode,
+                       int interp, int border, const uint8_t *value, hipStream_t stream);
+
+// The steps of a program as launches of the nine kernels above (vf_api.hip): `launches` is
 // vf_chain_plan.h's band_launches of a band or whole frame, masks[i] step i + 1's element when it
 // is a rank step, bufs[k] the address of buffer k's origin row (the band's row s0), out the rows a
 // chain::kOut launch writes; conv_form as launch_conv's form.  hist: the scratch of the program's

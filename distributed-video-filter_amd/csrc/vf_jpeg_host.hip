@@ -892,13 +892,16 @@ int Codec::run_filter_encode(bool fastdct, std::string *err) {
     if (k != 0) CK(b.ensure(dpix_bytes_));  // d_pix_ holds the decoded frames: sized by prepare_decode
     base[(size_t)k] = b.as<uint8_t>();
   }
-  uint32_t *hist = nullptr;  // a level or CLAHE step's scratch: the frames run in order on s_, so one set a step
+  // a level or CLAHE step's scratch: the frames run in order on s_, so one set a step (a warp step needs none)
+  uint32_t *hist = nullptr;
   if (chain::whole_frame(c.prog)) {
     for (const chain::Step &st : c.prog.steps) {
-      if (st.kind != chain::kClahe) continue;
+      if (st.kind != chain::kClahe && st.kind != chain::kWarp) continue;
       for (int f = 0; f < dn_; ++f) {
         std::string why;
-        if (!clahe::frame_ok((uint64_t)dfr_[(size_t)f].g.w, (uint64_t)dfr_[(size_t)f].g.h, st.tiles_x, st.tiles_y, &why)) {
+        const uint64_t fw = (uint64_t)dfr_[(size_t)f].g.w, fh = (uint64_t)dfr_[(size_t)f].g.h;
+        if (st.kind == chain::kClahe ? !clahe::frame_ok(fw, fh, st.tiles_x, st.tiles_y, &why)
+                                     : !warp::frame_ok(fw, fh, st.warp.mode, st.warp.m, &why)) {
           *err = "frame " + std::to_string(f) + ": " + why;
           return kInvalid;
         }

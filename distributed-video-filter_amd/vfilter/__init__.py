@@ -19,6 +19,9 @@ distributor.py).
                ``equalize_hist`` (the ``cv2.equalizeHist`` drop-in), ``auto_levels``, ``calc_hist`` (the
                histogram, counted on the GPU), ``Level``, ``level_frames`` and ``calc_hist_frames``
                ``clahe`` and ``create_clahe`` (the ``cv2.createCLAHE`` drop-in), ``Clahe`` and ``clahe_frames``
+               ``warp_affine``, ``flip`` and ``rotate`` (the ``cv2.warpAffine``, ``cv2.flip`` and ``cv2.rotate(ROTATE_180)``
+               drop-ins for frames that keep their size), ``Warp`` and ``warp_frames``
+  warps        builders of the usual affine maps (rotation, translation, zoom)
   colors       builders of the usual colour matrices (gray, swap_rb, sepia, saturation, gain, ...)
   kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
   elements     builders of the usual structuring elements (rect, cross)
@@ -27,7 +30,7 @@ distributor.py).
 The worker loop, the inverter plugin and the distributor live in ``worker``,
 ``inverter`` and ``distributor`` (imported on demand; they need no GPU to import).
 """
-from . import colors, elements, kernels, tables  # noqa: F401
+from . import colors, elements, kernels, tables, warps  # noqa: F401
 from ._lib import (ABI_VERSION, Context, VFilterError, device_count, get_context,  # noqa: F401
                    library_path, load_library)
 from .filters import (Chain, Combine, Mix, Morph, Rank, as_element, as_kernel, as_matrix, as_table,  # noqa: F401
@@ -38,6 +41,7 @@ from .filters import (Chain, Combine, Mix, Morph, Rank, as_element, as_kernel, a
 from .filters import Separable, as_taps, blur, box_filter, sep_filter2d, sep_frames  # noqa: F401
 from .filters import Level, auto_levels, calc_hist, calc_hist_frames, equalize_hist, level_frames  # noqa: F401
 from .filters import Clahe, clahe, clahe_frames, create_clahe  # noqa: F401
+from .filters import Warp, flip, rotate, warp_affine, warp_frames  # noqa: F401
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
@@ -49,4 +53,5 @@ __all__ = [
     "Separable", "as_taps", "sep_filter2d", "blur", "box_filter", "sep_frames",
     "Level", "equalize_hist", "auto_levels", "calc_hist", "calc_hist_frames", "level_frames",
     "Clahe", "clahe", "create_clahe", "clahe_frames",
+    "Warp", "warp_affine", "flip", "rotate", "warp_frames", "warps",
 ]

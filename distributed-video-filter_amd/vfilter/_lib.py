@@ -165,6 +165,16 @@ SIGNATURES = {
     "vf_jpeg_bench_clahe": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            _c_float_p, _c_float_p]),
+    "vf_warp_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "vf_warp_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, _vp]),
+    "vf_jpeg_warp": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_warp_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_warp": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
     "vf_binary_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
     "vf_chain_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
     "vf_jpeg_chain": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -181,6 +191,7 @@ STEP_SEP = 7                                                # VF_STEP_SEP: 6 sta
 STEP_LEVEL = 8                                              # VF_STEP_LEVEL: 9 stays refused as well
 LEVEL_EQUALIZE, LEVEL_STRETCH = 0, 1                        # VF_LEVEL_*
 STEP_CLAHE = 10                                             # VF_STEP_CLAHE: 11 stays refused as well
+STEP_WARP = 12                                              # VF_STEP_WARP: 13 stays refused as well
 CHAIN_MAX_STEPS = 8                                         # VF_CHAIN_MAX_STEPS
 ROUND_HALF_EVEN, ROUND_HALF_UP = 0, 1                       # VF_ROUND_*
 
@@ -643,6 +654,25 @@ class Context:
         self._check(self._lib.vf_clahe_device(self._ctx, dsrc or None, ddst or None, width, height, channels, clip_q8,
                                               tiles_x, tiles_y, mask, stream or None))
 
+    # -- the affine warp (cv2.warpAffine, cv2.flip): vf_warp_* -----------------------------------------------
+    @staticmethod
+    def _warp_args(m, mode: int, interp: int, border: int, value) -> tuple:
+        """``filters.Warp.args`` as the C arguments ``(m, mode, interp, border, value)``: six doubles and three ints."""
+        mm = (ctypes.c_double * 6)(*([float(v) for v in m] if m is not None else [0.0] * 6))
+        vv = (ctypes.c_int * 3)(*[int(v) for v in value])
+        return mm, int(mode), int(interp), int(border), vv
+
+    def warp_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                         channels: int, m, mode: int = 0, interp: int = 0, border: int = 2, value=(0, 0, 0)) -> None:
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
+        self._check(self._lib.vf_warp_frames_host(self._ctx, sa, da, wa, ha, n, channels,
+                                                  *self._warp_args(m, mode, interp, border, value)))
+
+    def warp_device(self, dsrc: int, ddst: int, width: int, height: int, channels: int, m, mode: int = 0,
+                    interp: int = 0, border: int = 2, value=(0, 0, 0), stream: int = 0) -> None:
+        self._check(self._lib.vf_warp_device(self._ctx, dsrc or None, ddst or None, width, height, channels,
+                                             *self._warp_args(m, mode, interp, border, value), stream or None))
+
     # -- filter chains (vf_chain_*, vf_binary_device) ------------------------------------------------
     def _steps(self, steps: Sequence):
         """``steps`` -- ``filters.Chain.args[0]``: tuples ``(kind, a, b, op, data, shift, border)`` with
@@ -675,6 +705,12 @@ class Context:
                 d = np.array([int(v) for v in data], np.int32)
                 if d.shape != (4,):
                     raise ValueError("a CLAHE step's data is (mask, clip_q8, tiles_x, tiles_y)")
+            elif kind == STEP_WARP:  # data: (m, mode, interp, value) -> six float64, then six int32
+                m, mode, interp, value = data
+                ints = np.array([int(mode), int(interp)] + [int(v) for v in value] + [0], np.int32)
+                d = np.frombuffer(np.array([float(v) for v in m], np.float64).tobytes() + ints.tobytes(), np.uint8)
+                if d.shape != (72,):
+                    raise ValueError("a warp step's data is (the six entries of m, mode, interp, the three border bytes)")
             else:
                 d = None
             if d is not None:
@@ -1242,6 +1278,34 @@ class Context:
         stage, as ``jpeg_bench_conv``'s)."""
         return self._jpeg_bench(self._lib.vf_jpeg_bench_clahe, (clip_q8, tiles_x, tiles_y, mask), "color", jpegs, quality,
                                 subsamp, flags, iters)
+
+    # -- JPEG with the affine warp in place of the inversion (vf_jpeg_warp*); tickets are invert tickets -----
+    def jpeg_warp(self, jpegs: Sequence, m, mode: int, interp: int, border: int, value, quality: int, subsamp: int,
+                  flags: int = 0) -> list:
+        """decode -> warp -> encode for every JPEG on the GPU; returns bytes."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_warp_submit(jpegs, m, mode, interp, border, value, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_warp_submit(self, jpegs: Sequence, m, mode: int, interp: int, border: int, value, quality: int,
+                         subsamp: int, flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the warp; collect with the ``jpeg_invert_result*`` methods."""
+        return self._jpeg_submit("jpeg_warp_submit", self._lib.vf_jpeg_warp_submit,
+                                 self._warp_args(m, mode, interp, border, value), jpegs, None, quality, subsamp, flags)
+
+    def jpeg_warp_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, m, mode: int, interp: int, border: int, value,
+                               quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_warp_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        return self._jpeg_submit("jpeg_warp_submit_addrs", self._lib.vf_jpeg_warp_submit,
+                                 self._warp_args(m, mode, interp, border, value), addrs, sizes, quality, subsamp, flags)
+
+    def jpeg_bench_warp(self, jpegs: Sequence, m, mode: int, interp: int, border: int, value, quality: int,
+                        subsamp: int, flags: int = 0, iters: int = 10):
+        """``jpeg_bench_invert`` with the warp between the decode and the encode (its time is in the total, not in a
+        stage, as ``jpeg_bench_conv``'s)."""
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_warp, self._warp_args(m, mode, interp, border, value), "color",
+                                jpegs, quality, subsamp, flags, iters)
 
     # -- JPEG with a filter chain in place of the inversion (vf_jpeg_chain*); tickets are invert tickets ----
     def jpeg_chain(self, jpegs: Sequence, steps: Sequence, quality: int, subsamp: int, flags: int = 0) -> list:

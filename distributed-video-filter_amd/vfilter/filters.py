@@ -1072,6 +1072,176 @@ def clahe_frames(frames: Sequence, f: Clahe, outs: Optional[List] = None, ctx: O
                         lambda *a: (ctx or get_context()).clahe_frames_host(*a, *f.args))
 
 
+# -- the affine warp: cv2.warpAffine, cv2.flip, cv2.rotate(ROTATE_180) ----------------------------------
+
+WARP_INTERPOLATIONS = {"linear": 0, "nearest": 1}  # the C ABI's interp
+WARP_FLIPS = {"h": 1, "v": 2, "both": 3, 1: 1, 0: 2, -1: 3}  # the C ABI's mode, by name and by cv2.flip's code
+INTER_NEAREST, INTER_LINEAR, WARP_INVERSE_MAP = 0, 1, 16  # cv2's flag values, for ``warp_affine(flags=...)``
+_SIZES_ARE_KEPT = "frames keep their size (resize, rotate by 90 degrees and dsize != frame size are not built)"
+
+
+def invert_affine(matrix) -> tuple:
+    """The map from destination to source of a forward 2 x 3 ``matrix``, by ``cv2.warpAffine``'s own formula in
+    its own order on Python floats (a singular matrix gives what cv2 gives: D = 0)."""
+    m0, m1, m2, m3, m4, m5 = matrix
+    d = m0 * m4 - m1 * m3
+    d = 1.0 / d if d != 0 else 0.0
+    a11 = m4 * d
+    a22 = m0 * d
+    m0 = a11
+    m1 *= -d
+    m3 *= -d
+    m4 = a22
+    b1 = -m0 * m2 - m1 * m5
+    b2 = -m3 * m2 - m4 * m5
+    return m0, m1, b1, m3, m4, b2
+
+
+def _warp_matrix(matrix) -> tuple:
+    try:
+        a = np.asarray(matrix, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"Warp: matrix is 2 x 3 numbers, not {matrix!r}") from None
+    if a.shape != (2, 3):
+        raise ValueError(f"Warp: matrix is 2 x 3, not shape {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError("Warp: every entry of matrix is finite")
+    return tuple(float(v) for v in a.reshape(6))
+
+
+def _warp_value(border_value) -> tuple:
+    try:
+        v = [border_value] * 3 if np.ndim(border_value) == 0 else list(border_value)
+        if len(v) == 4:  # a cv2 Scalar: B, G, R and an unused fourth
+            v = v[:3]
+        if len(v) != 3 or any(isinstance(x, (bool, np.bool_)) or int(x) != x for x in v):
+            raise TypeError
+        v = tuple(int(x) for x in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"Warp: border_value is an integer or (B, G, R) integers, not {border_value!r}") from None
+    if any(x < 0 or x > 255 for x in v):
+        raise ValueError(f"Warp: border_value = {border_value!r}; a byte is in 0 .. 255")
+    return v
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Warp:
+    """An affine warp that keeps the frame's size, ``cv2.warpAffine(src, matrix, (W, H))`` or ``cv2.flip``:
+    ``matrix`` is the 2 x 3 forward map as cv2 takes it (``inverse_map=True``: it already maps destination to source,
+    cv2's ``WARP_INVERSE_MAP``), or ``flip`` is "h", "v" or "both" (or cv2.flip's 1, 0, -1) and the map is resolved for
+    every frame's own size, so one value mirrors frames of mixed sizes.  ``interpolation`` "linear" or "nearest";
+    ``border`` "constant" (cv2.warpAffine's default, with ``border_value`` an integer or (B, G, R)), "replicate" or
+    "reflect101".  Bit-exact by the fixed-point rule of DESIGN.md 24."""
+    m: Optional[tuple]  # destination to source, six floats; None for a flip
+    mode: int
+    interpolation: str
+    interp_code: int
+    border: str
+    border_code: int
+    value: tuple
+    family = "warp"
+
+    def __init__(self, matrix=None, flip=None, interpolation="linear", border="constant", border_value=0,
+                 inverse_map=False):
+        if (matrix is None) == (flip is None):
+            raise ValueError("Warp: give exactly one of matrix and flip")
+        if flip is not None:
+            try:
+                mode = None if isinstance(flip, (bool, np.bool_)) else WARP_FLIPS.get(flip)
+            except TypeError:
+                mode = None
+            if mode is None:
+                raise ValueError(f"Warp: flip is \"h\", \"v\" or \"both\" (or cv2.flip's 1, 0, -1), not {flip!r}")
+            m = None
+        else:
+            mode = 0
+            m = _warp_matrix(matrix)
+            if not inverse_map:
+                m = tuple(float(v) for v in invert_affine(m))
+                if not all(np.isfinite(v) for v in m):
+                    raise ValueError("Warp: the inverse of matrix is not finite")
+        try:
+            icode = WARP_INTERPOLATIONS[interpolation]
+        except (KeyError, TypeError):
+            raise ValueError(f"Warp: interpolation must be one of {sorted(WARP_INTERPOLATIONS)}, not {interpolation!r}") from None
+        try:
+            bcode = BORDERS[border]
+        except (KeyError, TypeError):
+            raise ValueError(f"Warp: border must be one of {sorted(BORDERS)}, not {border!r}") from None
+        fields = {"m": m, "mode": mode, "interpolation": interpolation, "interp_code": icode, "border": border,
+                  "border_code": bcode, "value": _warp_value(border_value)}
+        for name, v in fields.items():
+            object.__setattr__(self, name, v)
+
+    @property
+    def args(self) -> tuple:
+        return self.m, self.mode, self.interp_code, self.border_code, self.value
+
+
+def _warp_one(name: str, src, f: Warp, dst, ctx) -> np.ndarray:
+    src = np.ascontiguousarray(_conv_frame(name, src))
+    dst = _rank_dst(name, src, dst)
+    channels = 1 if src.ndim == 2 else src.shape[2]
+    if src.size:
+        (ctx or get_context()).warp_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, *f.args)
+    return dst
+
+
+def _warp_flags(flags, inverse_map: bool) -> tuple:
+    """``flags`` -- "linear", "nearest" or cv2's integer (INTER_NEAREST 0, INTER_LINEAR 1, | WARP_INVERSE_MAP 16) -- as
+    (interpolation name, inverse_map)."""
+    if isinstance(flags, str):
+        return flags, inverse_map
+    if isinstance(flags, (bool, np.bool_)) or not isinstance(flags, (int, np.integer)) or int(flags) & ~(1 | WARP_INVERSE_MAP):
+        raise ValueError(f"warp_affine: flags is \"linear\", \"nearest\" or INTER_NEAREST / INTER_LINEAR with an optional "
+                         f"WARP_INVERSE_MAP, not {flags!r} (cubic, area and Lanczos are not built)")
+    return ("linear" if int(flags) & 1 else "nearest"), inverse_map or bool(int(flags) & WARP_INVERSE_MAP)
+
+
+def warp_affine(src: np.ndarray, M, dsize=None, flags="linear", border: str = "constant", border_value=0,
+                dst: Optional[np.ndarray] = None, inverse_map: bool = False, ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.warpAffine(src, M, (W, H), flags=..., borderMode=..., borderValue=...)`` on uint8 ``H x W`` or
+    ``H x W x 3`` input whose size is kept: ``dsize``, when given, must be the frame's ``(W, H)``.  ``dst`` as for
+    ``lut``; it may be ``src`` (the source is the staged copy)."""
+    interpolation, inverse = _warp_flags(flags, inverse_map)
+    f = Warp(M, None, interpolation, border, border_value, inverse)
+    a = _conv_frame("warp_affine", src)
+    if dsize is not None:
+        try:
+            same = tuple(int(v) for v in dsize) == (a.shape[1], a.shape[0]) and len(dsize) == 2
+        except (TypeError, ValueError):
+            same = False
+        if not same:
+            raise ValueError(f"warp_affine: dsize = {dsize!r} for a frame of (W, H) = ({a.shape[1]}, {a.shape[0]}); "
+                             + _SIZES_ARE_KEPT)
+    return _warp_one("warp_affine", src, f, dst, ctx)
+
+
+def flip(src: np.ndarray, code, dst: Optional[np.ndarray] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.flip(src, code)``: 0 flips around the x axis (vertically), 1 around the y axis
+    (horizontally), -1 both; "v", "h" and "both" name the same."""
+    if isinstance(code, (int, np.integer)) and not isinstance(code, (bool, np.bool_)):
+        code = 1 if code > 0 else -1 if code < 0 else 0  # cv2: any positive, any negative
+    return _warp_one("flip", src, Warp(flip=code, interpolation="nearest"), dst, ctx)
+
+
+def rotate(src: np.ndarray, code, dst: Optional[np.ndarray] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """``cv2.rotate(src, cv2.ROTATE_180)``: ``code`` "180" (or cv2's 1).  The 90 degree codes change the frame's shape
+    and are refused."""
+    if isinstance(code, (bool, np.bool_)) or code not in ("180", 1):
+        raise ValueError(f"rotate: code = {code!r}; " + _SIZES_ARE_KEPT)
+    return _warp_one("rotate", src, Warp(flip="both", interpolation="nearest"), dst, ctx)
+
+
+def warp_frames(frames: Sequence, f: Warp, outs: Optional[List] = None, ctx: Optional[Context] = None) -> List:
+    """A ``Warp`` over separately stored frames of one channel count and mixed sizes in one call.  Returns ndarrays
+    (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
+    if not isinstance(f, Warp):
+        raise ValueError("warp_frames: the filter is a Warp")
+    return _frames_call("warp_frames", [_conv_frame("warp_frames", a) for a in frames], outs,
+                        lambda *a: (ctx or get_context()).warp_frames_host(*a, *f.args))
+
+
 # -- filter chains: a program of filters between one upload and one download ----------------------
 
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
@@ -1079,6 +1249,7 @@ STEP_MIX = 5  # VF_STEP_MIX: 4 names no kind and stays refused
 STEP_SEP = 7  # VF_STEP_SEP: 6 stays refused as well
 STEP_LEVEL = 8  # VF_STEP_LEVEL: 9 stays refused as well
 STEP_CLAHE = 10  # VF_STEP_CLAHE: 11 stays refused as well
+STEP_WARP = 12  # VF_STEP_WARP: 13 stays refused as well
 BINARY_OPS = {"subtract": 0, "add": 1, "absdiff": 2, "min": 3, "max": 4}  # VF_BIN_*
 CHAIN_MAX_STEPS = 8  # VF_CHAIN_MAX_STEPS
 MORPH_OPS = ("erode", "dilate", "open", "close", "gradient", "tophat", "blackhat")
@@ -1091,7 +1262,7 @@ class Combine:
     """A two-input step of a ``Chain``: ``op(a, b)`` per byte, ``op`` one of "subtract"
     (``max(a - b, 0)``), "add" (``min(a + b, 255)``), "absdiff", "min", "max" -- ``cv2.subtract``,
     ``cv2.add``, ``cv2.absdiff``, ``cv2.min``, ``cv2.max`` on uint8.  ``a`` and ``b`` are each a filter
-    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``, ``Level``, ``Clahe``, another ``Combine``), a ``Chain``, or ``None``
+    value (``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``, ``Level``, ``Clahe``, ``Warp``, another ``Combine``), a ``Chain``, or ``None``
     for the value entering the ``Combine``; both are applied to that value."""
     op: str
     op_code: int
@@ -1126,9 +1297,11 @@ def _unary_step(f, a: int) -> tuple:
         return (STEP_LEVEL, a, 0, f.rule_code, (f.mask, int(f.link), f.clip_lo, f.clip_hi), 0, 0)
     if isinstance(f, Clahe):
         return (STEP_CLAHE, a, 0, 0, (f.mask, f.clip_q8, f.tiles_x, f.tiles_y), 0, 0)
-    # existing callers match the list up to "Chain" word for word, so a newer filter value is named after it
+    if isinstance(f, Warp):
+        return (STEP_WARP, a, 0, 0, (f.m if f.m is not None else (0.0,) * 6, f.mode, f.interp_code, f.value), 0, f.border_code)
+    # existing callers match the list up to "not <type>" word for word, so a newer filter value is named after it
     raise ValueError("chain: a step is Invert, Table, Kernel, Rank, Mix, Separable, Level, Combine or Chain, or a Clahe, "
-                     f"not {type(f).__name__}")
+                     f"not {type(f).__name__} (a Warp is a step as well)")
 
 
 def _check_program(steps: Sequence[tuple]) -> None:
@@ -1160,8 +1333,8 @@ class Chain:
     gives, every step with whole-frame borders.
 
     ``Chain(steps)``: each of ``steps`` -- ``Invert``, ``Table``, ``Kernel``, ``Rank``, ``Mix``, ``Separable``,
-    ``Level``, ``Clahe``, ``Combine`` or a nested ``Chain``, which is flattened -- is applied to the result of the one
-    before.  A chain with a ``Level`` or a ``Clahe`` reads whole frames: a frame larger than the context's staging is
+    ``Level``, ``Clahe``, ``Warp``, ``Combine`` or a nested ``Chain``, which is flattened -- is applied to the result of the one
+    before.  A chain with a ``Level``, a ``Clahe`` or a ``Warp`` reads whole frames: a frame larger than the context's staging is
     refused, not cut into bands.
     ``Chain.program(entries)`` takes the program itself: value 0 is the frame, value i the result of
     entry i (1-based); an entry is ``(filter value, a)`` or ``(binary op name, a, b)`` with ``a`` and
@@ -1220,7 +1393,7 @@ class Chain:
         return len(self.steps)
 
 
-_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable, Level, Clahe)
+_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable, Level, Clahe, Warp)
 
 
 def _lower(item, cur: int, prog: List[tuple]) -> int:

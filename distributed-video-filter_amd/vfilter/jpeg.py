@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import Clahe, Invert, Kernel, Level, Morph, Rank, Separable, Table, _as_chain, _as_mix
+from .filters import Clahe, Invert, Kernel, Level, Morph, Rank, Separable, Table, Warp, _as_chain, _as_mix, _warp_flags
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -94,7 +94,7 @@ class TurboJPEG:
         return self.ctx.jpeg_encode(list(imgs), pixel_format, quality, jpeg_subsample,
                                     self._enc_flags(flags, quality))
 
-    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank, Mix, Separable, Level, Clahe, Chain) between decode and encode.  The
+    # One filter value (``vfilter.filters``: Invert, Table, Kernel, Rank, Mix, Separable, Level, Clahe, Warp, Chain) between decode and encode.  The
     # ``invert*``, ``lut*`` and ``filter2d*`` methods below are these three with their filter built
     # from the call's own arguments.
     def filter_batch(self, jpeg_bufs: Sequence, filt, quality: int = 85, jpeg_subsample: int = TJSAMP_422,
@@ -284,6 +284,22 @@ class TurboJPEG:
     def clahe_batch(self, jpeg_bufs: Sequence, clip_limit=40.0, tile_grid_size=(8, 8), channels=None, quality: int = 85,
                     jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
         return self.filter_batch(jpeg_bufs, Clahe(clip_limit, tile_grid_size, channels), quality, jpeg_subsample, flags)
+
+    # -- the affine warp (cv2.warpAffine, cv2.flip) between decode and encode ---------------------------------
+    # The batch and submit forms go through ``filter_batch*`` with a ``vfilter.filters.Warp``.
+    def warp_affine(self, jpeg_buf, M, flags="linear", border: str = "constant", border_value=0, inverse_map: bool = False,
+                    quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags_tj: int = 0) -> bytes:
+        """``encode(vfilter.warp_affine(decode(jpeg_buf), M, ...))`` on the GPU, the pixels never leaving it; the
+        frame keeps its size.  ``flags`` as ``vfilter.warp_affine``'s; ``flags_tj``: the TurboJPEG flags."""
+        interpolation, inverse = _warp_flags(flags, inverse_map)
+        return self.filter_batch([jpeg_buf], Warp(M, None, interpolation, border, border_value, inverse), quality,
+                                 jpeg_subsample, flags_tj)[0]
+
+    def flip(self, jpeg_buf, code, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(cv2.flip(decode(jpeg_buf), code))`` on the GPU: ``code`` 0, 1, -1 or "v", "h", "both"."""
+        if isinstance(code, (int, np.integer)) and not isinstance(code, (bool, np.bool_)):
+            code = 1 if code > 0 else -1 if code < 0 else 0
+        return self.filter_batch([jpeg_buf], Warp(flip=code, interpolation="nearest"), quality, jpeg_subsample, flags)[0]
 
     # -- a filter chain (vfilter.filters.Chain) between one decode and one encode ------------------------
     def chain(self, jpeg_buf, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:

@@ -649,6 +649,61 @@ int vf_jpeg_bench_clahe(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *
                         int clip_q8, int tiles_x, int tiles_y, int mask, int quality, int subsamp,
                         int flags, int iters, float *ms, float *stage_ms);
 
+/* ---- the affine warp (cv2.warpAffine, cv2.flip) -------------------------------------------------
+ * Every output pixel (y, x) of a uint8 frame of 1 or 3 interleaved channels reads the source at
+ * sx = m0 x + m1 y + m2, sy = m3 x + m4 y + m5, m the map FROM DESTINATION TO SOURCE (cv2's
+ * WARP_INVERSE_MAP form; cv2.invertAffineTransform of a forward map), in the fixed point of OpenCV
+ * 3.x .. 4.10 imgwarp.cpp for 8-bit frames (bit-exact by the rule below).  The frame
+ * keeps its size.
+ *   m       six finite doubles; read when mode is 0.
+ *   mode    0: the given m; 1: flip horizontal, 2: flip vertical, 3: both, resolved per frame of
+ *           W x H to {-1, 0, W-1, 0, 1, 0}, {1, 0, 0, 0, -1, H-1} and {-1, 0, W-1, 0, -1, H-1}.
+ *   interp  0: linear (cv2.INTER_LINEAR), 1: nearest (cv2.INTER_NEAREST).
+ *   border  a VF_BORDER_*; value: three ints 0 .. 255, the constant border's byte per channel
+ *           (cv2's borderValue; a 1-channel frame uses value[0]).
+ * Every double operation is rounded separately, none fused; rint rounds half to even:
+ *   adelta(x) = int(rint((m0 x) 1024)), bdelta(x) = int(rint((m3 x) 1024)),
+ *   X0(y) = int(rint((m1 y + m2) 1024)) + rd, Y0(y) = int(rint((m4 y + m5) 1024)) + rd,
+ *   rd = 16 for linear, 512 for nearest.
+ * Linear: X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5 (arithmetic), sx = clamp(X >> 5, -32768,
+ * 32767), fx = X & 31, the same in y; the taps (sy, sx), (sy, sx+1), (sy+1, sx), (sy+1, sx+1) weigh
+ * 32 (32-fx)(32-fy), 32 fx (32-fy), 32 (32-fx) fy, 32 fx fy (sum 32768); dst = (sum + 16384) >> 15.
+ * Nearest: sx = clamp((X0 + adelta) >> 10, -32768, 32767), the same in y; dst is the tap (sy, sx).
+ * A tap: each axis goes through the border rule on its own; under VF_BORDER_CONSTANT a tap with
+ * either index outside the frame is value[c], decided tap by tap.
+ * Limits, VF_E_INVALID with the reason before any GPU work: sides of at most 32767; per frame
+ * |m0| (W-1) 1024, |m3| (W-1) 1024 and |m1 y + m2| 1024 + 512 at y = 0 and y = H-1 (and the same
+ * for m4, m5) each below 2^30.  The empty frame is a no-op. */
+
+/* Enqueue the filter on `stream` over one device-resident frame: any alignment; ddst must not
+ * overlap dsrc (an output pixel reads anywhere); returns after the launch. */
+int vf_warp_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                   const double *m, int mode, int interp, int border, const int *value,
+                   void *stream);
+
+/* The filter on `n` separately allocated host frames of mixed sizes and one channel count,
+ * synchronous; srcs[i] == dsts[i] is allowed (the source is the staged copy).  A frame that does
+ * not fit the context's staging whole is refused: a frame is never cut into bands. */
+int vf_warp_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                        const int *widths, const int *heights, int n, int channels,
+                        const double *m, int mode, int interp, int border, const int *value);
+
+/* vf_jpeg_invert with the filter in place of the inversion: decode -> warp -> encode on the GPU,
+ * on the decoded 3-channel BGR frame (grayscale inputs included). */
+int vf_jpeg_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                 const double *m, int mode, int interp, int border, const int *value, int quality,
+                 int subsamp, int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the filter.  The ticket is an invert ticket. */
+int vf_jpeg_warp_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                        const double *m, int mode, int interp, int border, const int *value,
+                        int quality, int subsamp, int flags, uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the filter between the decode and the encode. */
+int vf_jpeg_bench_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                       const double *m, int mode, int interp, int border, const int *value,
+                       int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms);
+
 /* ---- filter chains (cv2.morphologyEx, difference of blurs, ...) -----------------------------
  * A program is a straight-line list of 1 .. VF_CHAIN_MAX_STEPS steps over values.
  * Value 0 is the input frame (uint8, 1 or 3 interleaved channels, packed rows), value i the result
@@ -671,13 +726,17 @@ int vf_jpeg_bench_clahe(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *
  *                   only: vf_chain_frames_host refuses a frame that does not fit the staging whole
  *   VF_STEP_CLAHE   CLAHE: `data` 4 int32 {mask, clip_q8, tiles_x, tiles_y}.  It reads its whole
  *                   operand as well, with the same refusal
+ *   VF_STEP_WARP    the affine warp: `data` six float64 m, then six int32 {mode, interp, value B,
+ *                   G, R, 0} (48 + 24 bytes), with `border`.  It reads anywhere in its operand: the
+ *                   same refusal, and it never runs in place
  * `data` is a HOST pointer, read during the call only.  VF_E_INVALID, before any GPU work: a step
  * that reads a later value or itself, a value other than the last that no step reads, a 3-channel
  * table or a colour matrix on 1-channel frames, more than VF_CHAIN_MAX_STEPS steps, and anything
  * the single-filter entry points refuse for a table, a kernel, an element or a matrix.
  * The VF_STEP_* values are not dense: 4 names no kind and stays refused ("unknown kind 4"), as
  * callers' checks of the refusal expect, so VF_STEP_MIX is 5; 6 likewise, so VF_STEP_SEP is 7 and
- * VF_STEP_LEVEL 8; 9 stays refused too, so VF_STEP_CLAHE is 10, and 11 stays refused. */
+ * VF_STEP_LEVEL 8; 9 stays refused too, so VF_STEP_CLAHE is 10; 11 stays refused, so
+ * VF_STEP_WARP is 12, and 13 stays refused. */
 #define VF_STEP_TABLE  0
 #define VF_STEP_CONV   1
 #define VF_STEP_RANK   2
@@ -686,6 +745,7 @@ int vf_jpeg_bench_clahe(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *
 #define VF_STEP_SEP    7
 #define VF_STEP_LEVEL  8
 #define VF_STEP_CLAHE  10
+#define VF_STEP_WARP   12
 #define VF_BIN_SUBTRACT 0
 #define VF_BIN_ADD      1
 #define VF_BIN_ABSDIFF  2
@@ -698,10 +758,11 @@ typedef struct vf_step {
   int a, b;         /* operand values; b for VF_STEP_BINARY only */
   int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_*; VF_STEP_MIX, VF_STEP_SEP: a VF_ROUND_*; VF_STEP_LEVEL: a VF_LEVEL_* */
   const void *data; /* the table, the int16 weights, the element or the int32 of a matrix, of
-                       separable taps, of a level step or of a CLAHE step (host memory) */
+                       separable taps, of a level step or of a CLAHE step, or a warp step's
+                       doubles and int32 (host memory) */
   int kw, kh;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP */
   int shift;        /* VF_STEP_CONV, VF_STEP_MIX, VF_STEP_SEP */
-  int border;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP: a VF_BORDER_* */
+  int border;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP, VF_STEP_WARP: a VF_BORDER_* */
   int channels;     /* VF_STEP_TABLE: 1 or 3 */
 } vf_step;
 
