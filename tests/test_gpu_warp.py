@@ -6,7 +6,9 @@ Sizes (W x H): 1 x 1, 1 x 9, 9 x 1 and 2 x 2 have axes on which a saturated coor
 tiles on both axes, so a rotation about the centre gives tiles whose source box is inside the frame (staged in LDS)
 and tiles that touch the border (gathered from global memory) in one frame.  300 x 80 under the 0.25 x shrink has a
 box inside the frame that is over the LDS budget on three channels.  Every case runs again with ``VF_WARP_LDS=0``,
-which forces the general path everywhere; the references are computed once and shared.
+which forces the general path everywhere; the references are computed once and shared.  70 x 130 and the map
+``rows_x2`` are there for ``test_the_tile_switches_change_no_byte``, which sets ``VF_WARP_ROWS`` and ``VF_WARP_LDS``
+(``tests/test_warp_tile_switches.py`` holds, without a GPU, what those cases reach).
 """
 import ctypes
 import os
@@ -43,6 +45,8 @@ def _maps(w, h):
         "shrink_0.25": (0, [4, 0, 0, 0, 4, 0]),
         "saturating": (0, [1, 0, 999999, 0, 1, -999998]),
         "negative_determinant": (0, [0.6, 0.8, -3.5, 0.8, -0.6, 2.5]),
+        # two source rows an output row: a tile of 64 rows reads a box of 128, more than the default LDS budget holds
+        "rows_x2": (0, [1, 0, 0.25, 0, 2, 0.5]),
     }
 
 
@@ -107,21 +111,76 @@ def test_every_size_map_and_border_on_the_general_path(vf_ctx, general_path, int
     _every_case(vf_ctx, c, interp)
 
 
-def _tile_paths(w, h, c, m, interp):
-    """Per tile of the output: "lds", "border" (the box leaves the frame) or "budget", from the reference's coordinates."""
+MAX_ROWS, MAX_LDS = 64, 61440  # csrc/vf_warp.hip kMaxTileRows, kMaxWarpLds
+# (VF_WARP_ROWS, VF_WARP_LDS): 100 rows clamp to 64 and 0 to 1; 1000 bytes round down to 992 and 1000000 clamp to the
+# cap; 16 bytes hold a box of one row of at most 16 bytes, so nearly every tile takes the general path.  64 rows
+# meet both large budgets, where the dynamic LDS and the row bases together come close to 64 KiB.
+SWITCHES = [(1, 16), (1, 61440), (5, 16), (5, 1000), (16, 61440), (64, 1000), (64, 61440), (64, 1000000), (100, 16),
+            (100, 1000000), (0, 1000), (0, 61440)]
+SWITCH_SIZES = [(TILE_W + 1, TILE_H + 1), (67, 35), (160, 48), (70, 130)]  # 70 x 130: a full tile of 64 rows, and a third row of tiles
+SWITCH_MAPS = ["rotate30_scale1.3", "shrink_0.25", "shift_32nds", "flip_both", "rows_x2"]
+
+
+def _clamped(rows, lds):
+    """What ``launch_warp`` makes of the two switches."""
+    return min(max(rows, 1), MAX_ROWS), min(lds, MAX_LDS) // 16 * 16
+
+
+@pytest.fixture
+def tile_switches():
+    """A setter of ``VF_WARP_ROWS`` and ``VF_WARP_LDS``, which the library reads at every launch; both are put back."""
+    old = {k: os.environ.get(k) for k in ("VF_WARP_ROWS", "VF_WARP_LDS")}
+
+    def set_both(rows, lds):
+        os.environ["VF_WARP_ROWS"], os.environ["VF_WARP_LDS"] = str(rows), str(lds)
+
+    yield set_both
+    for k, v in old.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+
+
+@pytest.mark.parametrize("c", [1, 3])
+@pytest.mark.parametrize("interp", [R.LINEAR, R.NEAREST])
+def test_the_tile_switches_change_no_byte(vf_ctx, tile_switches, interp, c):
+    """A tile of 1 to 64 rows under a budget of 16 bytes to the cap, against the same references: a switch may
+    change the path a tile takes, never a byte."""
+    for rows, lds in SWITCHES:
+        tile_switches(rows, lds)
+        for w, h in SWITCH_SIZES + [(300, 80)]:
+            img = _frame(w, h, c)
+            for name in SWITCH_MAPS if (w, h) != (300, 80) else ["shrink_0.25"]:
+                mode, m = _maps(w, h)[name]
+                for border in BORDER_NAMES:
+                    out = vfilter.warp_frames([img], _filter(mode, m, interp, border), ctx=vf_ctx)[0]
+                    want = _want(w, h, c, name, interp, border)
+                    assert out.shape == img.shape and np.array_equal(out, want), \
+                        (rows, lds, w, h, name, border, np.argwhere(out != want)[:5])
+
+
+def _tile_boxes(w, h, c, m, interp, rows=TILE_H, budget=LDS):
+    """Per tile of the output, a tile ``rows`` rows under a budget of ``budget`` bytes: ("lds", "border" (the box
+    leaves the frame) or "budget", the bytes of its box in LDS), from the reference's coordinates."""
     sx, sy, _, _ = R.coords(m, w, h, interp)
     second = 1 if interp == R.LINEAR else 0
     out = []
-    for y0 in range(0, h, TILE_H):
+    for y0 in range(0, h, rows):
         for x0 in range(0, w, TILE_W):
-            bx, by = sx[y0:y0 + TILE_H, x0:x0 + TILE_W], sy[y0:y0 + TILE_H, x0:x0 + TILE_W]
+            bx, by = sx[y0:y0 + rows, x0:x0 + TILE_W], sy[y0:y0 + rows, x0:x0 + TILE_W]
             lo_x, hi_x, lo_y, hi_y = bx.min(), bx.max() + second, by.min(), by.max() + second
             if lo_x < 0 or hi_x >= w or lo_y < 0 or hi_y >= h:
-                out.append("border")
+                out.append(("border", 0))
             else:
                 pitch = ((hi_x - lo_x + 1) * c + 15) // 16 * 16
-                out.append("lds" if pitch * (hi_y - lo_y + 1) <= LDS else "budget")
+                size = int(pitch * (hi_y - lo_y + 1))
+                out.append(("lds" if size <= budget else "budget", size))
     return out
+
+
+def _tile_paths(w, h, c, m, interp, rows=TILE_H, budget=LDS):
+    return [path for path, _ in _tile_boxes(w, h, c, m, interp, rows, budget)]
 
 
 def test_the_frames_are_what_they_are_chosen_for():
