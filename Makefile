@@ -22,8 +22,8 @@ vfdist: $(DLIB)
 $(DLIB): $(CSRC)/vf_dist.cc $(CSRC)/vf_json.h include/vfdist.h
 	$(CXX) -O2 -g -std=c++17 -fPIC -shared -pthread -Wall -Wextra -Iinclude -fvisibility=hidden -Wl,--no-undefined $< -o $@ -lrt
 
-SRCS := $(CSRC)/vf_kernels.hip $(CSRC)/vf_engine.hip $(CSRC)/vf_api.hip $(CSRC)/vf_jpeg_kernels.hip $(CSRC)/vf_jpeg_host.hip $(CSRC)/vf_lut.hip $(CSRC)/vf_conv.hip $(CSRC)/vf_rank.hip $(CSRC)/vf_binary.hip $(CSRC)/vf_mix.hip $(CSRC)/vf_sep.hip $(CSRC)/vf_level.hip $(CSRC)/vf_clahe.hip $(CSRC)/vf_warp.hip
-HDRS := $(CSRC)/vf_internal.h $(CSRC)/vf_stream.h $(CSRC)/vf_stream_split.h $(CSRC)/vf_pixel_split.h $(CSRC)/vf_lut_split.h $(CSRC)/vf_conv_border.h $(CSRC)/vf_conv_bands.h $(CSRC)/vf_chain_plan.h $(CSRC)/vf_rank_net.h $(CSRC)/vf_tile.h $(CSRC)/vf_tile_plan.h $(CSRC)/vf_sep_plan.h $(CSRC)/vf_level_plan.h $(CSRC)/vf_clahe_plan.h $(CSRC)/vf_warp_plan.h $(CSRC)/vf_lut_lds.h $(CSRC)/vf_host_mem.h $(CSRC)/vf_env.h $(CSRC)/vf_jpeg_plan.h $(CSRC)/vf_jpeg.h $(CSRC)/vf_jpeg_types.h $(CSRC)/vf_jpeg_parse.h $(CSRC)/vf_jpeg_codec.h include/vfilter.h
+SRCS := $(CSRC)/vf_kernels.hip $(CSRC)/vf_engine.hip $(CSRC)/vf_api.hip $(CSRC)/vf_jpeg_kernels.hip $(CSRC)/vf_jpeg_host.hip $(CSRC)/vf_lut.hip $(CSRC)/vf_conv.hip $(CSRC)/vf_rank.hip $(CSRC)/vf_binary.hip $(CSRC)/vf_mix.hip $(CSRC)/vf_sep.hip $(CSRC)/vf_level.hip $(CSRC)/vf_clahe.hip $(CSRC)/vf_warp.hip $(CSRC)/vf_resize.hip
+HDRS := $(CSRC)/vf_internal.h $(CSRC)/vf_stream.h $(CSRC)/vf_stream_split.h $(CSRC)/vf_pixel_split.h $(CSRC)/vf_lut_split.h $(CSRC)/vf_conv_border.h $(CSRC)/vf_conv_bands.h $(CSRC)/vf_chain_plan.h $(CSRC)/vf_rank_net.h $(CSRC)/vf_tile.h $(CSRC)/vf_tile_plan.h $(CSRC)/vf_sep_plan.h $(CSRC)/vf_level_plan.h $(CSRC)/vf_clahe_plan.h $(CSRC)/vf_warp_plan.h $(CSRC)/vf_resize_plan.h $(CSRC)/vf_lut_lds.h $(CSRC)/vf_host_mem.h $(CSRC)/vf_env.h $(CSRC)/vf_jpeg_plan.h $(CSRC)/vf_jpeg.h $(CSRC)/vf_jpeg_types.h $(CSRC)/vf_jpeg_parse.h $(CSRC)/vf_jpeg_codec.h include/vfilter.h
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(LDFLAGS) -pthread $(SRCS) -o $@

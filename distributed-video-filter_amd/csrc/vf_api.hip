@@ -35,6 +35,7 @@
 #include "vf_sep_plan.h"
 #include "vf_level_plan.h"
 #include "vf_clahe_plan.h"
+#include "vf_resize_plan.h"
 #include "vf_warp_plan.h"
 #include "vf_jpeg_codec.h"
 #include "vf_lut_split.h"
@@ -560,9 +561,17 @@ namespace vf {
 hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const std::vector<chain::Launch> &launches,
                         uint8_t *const *bufs, uint8_t *out, int w, int channels, int frame_h, int conv_form,
                         uint32_t *hist, const LaunchCfg &cfg, hipStream_t stream) {
-  const size_t row = (size_t)w * (size_t)channels;
+  const int frame_w = w, frame_rows = frame_h;
   for (const chain::Launch &l : launches) {
     const chain::Step &s = prog.steps[(size_t)l.step - 1];
+    // a program with a resize step (chain::frame_launches): every value has a size of its own, and
+    // the launch says its operand's, which is the result's too for every step but the resize
+    if (l.a_w) w = l.a_w, frame_h = l.a_h;
+    else w = frame_w, frame_h = frame_rows;
+    // `row` is the OPERAND's pitch.  It addresses dst as well because every step but the resize makes a value of
+    // its operand's size, and a resize launch comes from frame_launches, whose row offsets are all 0 (dst_row * row
+    // is 0 whatever the pitch) and whose kernel takes the result's size from the step, not from nbytes.
+    const size_t row = (size_t)w * (size_t)channels;
     const uint8_t *a = bufs[l.a_buf] + (size_t)l.a_row * row;
     uint8_t *dst = l.dst_buf == chain::kOut ? out : bufs[l.dst_buf] + (size_t)l.dst_row * row;
     const size_t nbytes = (size_t)l.nrows * row;
@@ -597,6 +606,10 @@ hipError_t run_launches(const chain::Program &prog, const uint64_t *masks, const
       e = l.nrows == frame_h && a != dst
               ? launch_warp(a, dst, w, frame_h, channels, s.warp.m, s.warp.mode, s.warp.interp, s.border, s.warp.value, stream)
               : hipErrorInvalidValue;
+    else if (s.kind == chain::kResize)  // whole frames only; never in place; the launch carries both sizes
+      e = l.a_w && a != dst ? launch_resize(a, dst, l.a_w, l.a_h, channels, s.resize.dw, s.resize.dh, s.resize.fx, s.resize.fy,
+                                            s.resize.interp, stream)
+                            : hipErrorInvalidValue;
     else
       e = hipErrorInvalidValue;  // no kernel for the kind: validate() lets none through
     if (e != hipSuccess) return e;
@@ -626,6 +639,8 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
   if (rc != VF_OK) return rc;
   const int ry = vf::chain::reach(prog);
   const bool whole = vf::chain::whole_frame(prog);  // a level step: every frame is one band, or refused
+  const bool sized = vf::chain::has_resize(prog);   // a resize step: a size per value, the result's is not the frame's
+  std::vector<std::vector<vf::chain::Size>> sizes((size_t)(n > 0 ? n : 0));  // sized: of frame i's values
   if (n < 0) return set_err(ctx, VF_E_INVALID, 0, "%s: n < 0", fn);
   if (n > 0 && (!srcs || !dsts || !widths || !heights)) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL array", fn);
   // one upload + launch + download per band (vf_conv_bands.h); most frames are one band
@@ -642,24 +657,53 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
     if ((rc = check_frame_shape(ctx, fn, widths[i], heights[i], channels)) != VF_OK) return rc;
     if (!srcs[i] || !dsts[i]) return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d has a NULL buffer", fn, i);
     const size_t row = (size_t)widths[i] * (size_t)channels;
-    if (overlaps_partially(srcs[i], dsts[i], row * (size_t)heights[i]))
-      return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d src/dst partially overlap", fn, i);
     std::vector<vf::conv::Band> bs;
+    if (sized) {
+      std::string why;
+      if (!vf::chain::value_sizes(prog, widths[i], heights[i], &sizes[(size_t)i], &why))
+        return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
+      const vf::chain::Size out = sizes[(size_t)i].back();
+      const size_t in_bytes = row * (size_t)heights[i], out_bytes = (size_t)out.w * (size_t)out.h * (size_t)channels;
+      if (out.w == widths[i] && out.h == heights[i]) {
+        if (overlaps_partially(srcs[i], dsts[i], in_bytes))
+          return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d src/dst partially overlap", fn, i);
+      } else if (srcs[i] < dsts[i] + out_bytes && dsts[i] < srcs[i] + in_bytes) {
+        return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: src (%d x %d) and dst (%d x %d) overlap; frames of two sizes do not share memory",
+                       fn, i, widths[i], heights[i], out.w, out.h);
+      }
+      for (size_t v = 0; v < sizes[(size_t)i].size(); ++v) {
+        const vf::chain::Size z = sizes[(size_t)i][v];
+        if ((size_t)z.w * (size_t)z.h * (size_t)channels > cap)
+          return set_err(ctx, VF_E_INVALID, 0,
+                         "%s: frame %d: value %zu of %d x %d (%zu bytes) does not fit the context's %zu-byte staging (a resize "
+                         "step reads the whole frame: it is not cut into bands)",
+                         fn, i, v, z.w, z.h, (size_t)z.w * (size_t)z.h * (size_t)channels, cap);
+      }
+    } else if (overlaps_partially(srcs[i], dsts[i], row * (size_t)heights[i])) {
+      return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d src/dst partially overlap", fn, i);
+    }
     if (whole) {
       std::string why;
-      for (const vf::chain::Step &s : prog.steps)
-        if (s.kind == vf::chain::kLevel &&
-            !vf::level::pixels_ok((uint64_t)widths[i] * (uint64_t)heights[i], s.mask, s.link, channels, &why))
+      for (const vf::chain::Step &s : prog.steps) {
+        // the step's operand: the frame, or under a resize step the value's own size
+        const uint64_t vw = (uint64_t)(sized ? sizes[(size_t)i][(size_t)s.a].w : widths[i]),
+                       vh = (uint64_t)(sized ? sizes[(size_t)i][(size_t)s.a].h : heights[i]);
+        if (s.kind == vf::chain::kLevel && !vf::level::pixels_ok(vw * vh, s.mask, s.link, channels, &why))
           return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
-      for (const vf::chain::Step &s : prog.steps)
-        if (s.kind == vf::chain::kClahe &&
-            !vf::clahe::frame_ok((uint64_t)widths[i], (uint64_t)heights[i], s.tiles_x, s.tiles_y, &why))
+      }
+      for (const vf::chain::Step &s : prog.steps) {
+        const uint64_t vw = (uint64_t)(sized ? sizes[(size_t)i][(size_t)s.a].w : widths[i]),
+                       vh = (uint64_t)(sized ? sizes[(size_t)i][(size_t)s.a].h : heights[i]);
+        if (s.kind == vf::chain::kClahe && !vf::clahe::frame_ok(vw, vh, s.tiles_x, s.tiles_y, &why))
           return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
-      for (const vf::chain::Step &s : prog.steps)
-        if (s.kind == vf::chain::kWarp &&
-            !vf::warp::frame_ok((uint64_t)widths[i], (uint64_t)heights[i], s.warp.mode, s.warp.m, &why))
+      }
+      for (const vf::chain::Step &s : prog.steps) {
+        const uint64_t vw = (uint64_t)(sized ? sizes[(size_t)i][(size_t)s.a].w : widths[i]),
+                       vh = (uint64_t)(sized ? sizes[(size_t)i][(size_t)s.a].h : heights[i]);
+        if (s.kind == vf::chain::kWarp && !vf::warp::frame_ok(vw, vh, s.warp.mode, s.warp.m, &why))
           return set_err(ctx, VF_E_INVALID, 0, "%s: frame %d: %s", fn, i, why.c_str());
-      if (row * (size_t)heights[i] > cap)
+      }
+      if (!sized && row * (size_t)heights[i] > cap)  // sized: every value was checked above, the frame among them
         return set_err(ctx, VF_E_INVALID, 0,
                        "%s: frame %d: %d rows of %zu bytes do not fit the context's %zu-byte staging (a level step "
                        "reads the whole frame: it is not cut into bands)",
@@ -682,7 +726,10 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
   VF_HIP(ctx, hipSetDevice(ctx->device));
   const size_t alloc = ((cap + 15 + 15) & ~(size_t)15);
   if ((rc = raw_staging(ctx, fn, alloc)) != VF_OK) return rc;
-  const vf::chain::Buffers bufs = vf::chain::assign_buffers(prog);
+  // Buffer 0 is a piece's upload slot in raw_din, as large as the frame and followed by the next piece's.  Under a
+  // resize step a later value may be larger than the frame, so buffer 0 is kept for value 0 alone (keep_input):
+  // every other value lives in a scratch buffer of `alloc` bytes, and every value was checked against cap above.
+  const vf::chain::Buffers bufs = vf::chain::assign_buffers(prog, sized);
   while ((int)ctx->raw_scratch.size() < vf::chain::scratch_buffers(bufs, prog, true)) {
     void *p = nullptr;
     VF_HIP(ctx, hipMalloc(&p, alloc));
@@ -708,7 +755,9 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
     for (; j < pieces.size(); ++j) {
       const Piece &p = pieces[j];
       const size_t row = (size_t)widths[p.frame] * (size_t)channels;
-      const size_t in_bytes = (size_t)(p.b.s1 - p.b.s0) * row, out_bytes = (size_t)(p.b.y1 - p.b.y0) * row;
+      const size_t in_bytes = (size_t)(p.b.s1 - p.b.s0) * row;
+      const size_t out_bytes = sized ? (size_t)sizes[(size_t)p.frame].back().w * (size_t)sizes[(size_t)p.frame].back().h * (size_t)channels
+                                     : (size_t)(p.b.y1 - p.b.y0) * row;
       if (cin + in_bytes > alloc || cout + out_bytes > alloc) break;
       uint8_t *din = ctx->raw_din + cin, *dout = ctx->raw_dout + cout;
       const uint8_t *src = srcs[p.frame];
@@ -720,7 +769,9 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
       VF_HIP(ctx, hipMemcpyAsync(din + head, src + (size_t)p.b.s0 * row + head, in_bytes - head, hipMemcpyHostToDevice, st));
       base[0] = din;
       const int w = widths[p.frame], h = heights[p.frame];
-      VF_HIP(ctx, vf::run_launches(prog, masks.data(), vf::chain::band_launches(prog, bufs, h, p.b.y0, p.b.y1, p.b.s0, true),
+      VF_HIP(ctx, vf::run_launches(prog, masks.data(),
+                                   sized ? vf::chain::frame_launches(prog, bufs, sizes[(size_t)p.frame], true)
+                                         : vf::chain::band_launches(prog, bufs, h, p.b.y0, p.b.y1, p.b.s0, true),
                                    base, dout, w, channels, h, form, whole ? ctx->level_hist : nullptr, ctx->cfg, st));
       at[j] = cout;
       cin += (in_bytes + 15) & ~(size_t)15;
@@ -729,6 +780,12 @@ int program_frames_host(vf_ctx *ctx, const char *fn, const uint8_t *const *srcs,
     for (size_t k = i; k < j; ++k) {
       const Piece &p = pieces[k];
       const size_t row = (size_t)widths[p.frame] * (size_t)channels;
+      if (sized) {  // one band, the result's size
+        const vf::chain::Size out = sizes[(size_t)p.frame].back();
+        VF_HIP(ctx, hipMemcpyAsync(dsts[p.frame], ctx->raw_dout + at[k], (size_t)out.w * (size_t)out.h * (size_t)channels,
+                                   hipMemcpyDeviceToHost, st));
+        continue;
+      }
       VF_HIP(ctx, hipMemcpyAsync(dsts[p.frame] + (size_t)p.b.y0 * row, ctx->raw_dout + at[k],
                                  (size_t)(p.b.y1 - p.b.y0) * row, hipMemcpyDeviceToHost, st));
     }
@@ -1176,7 +1233,91 @@ VF_EXPORT int vf_warp_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8
   return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
 }
 
-// ---- filter chains: a program of table / conv / rank / binary / mix / sep / level / clahe / warp steps on raw frames
+// ---- the resize (cv2.resize) on raw frames -------------------------------------------------------------
+
+namespace {
+
+// The filter arguments every vf_resize_* / vf_jpeg_resize* entry point and a VF_STEP_RESIZE step share
+// (vf_resize_plan.h has the limits).
+int check_resize(vf_ctx *ctx, const char *fn, int dw, int dh, double fx, double fy, int interp, int channels) {
+  std::string why;
+  if (!vf::resize::limits_ok(dw, dh, fx, fy, interp, channels, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  return VF_OK;
+}
+
+// A VF_STEP_RESIZE step's data (include/vfilter.h): two float64, then {dw, dh, interp, 0}.
+struct ResizeStepData {
+  double f[2];
+  int32_t i[4];
+};
+static_assert(sizeof(ResizeStepData) == vf::resize::kStepBytes, "the step's data is packed");
+
+ResizeStepData resize_step_data(int dw, int dh, double fx, double fy, int interp) {
+  ResizeStepData d = {};
+  d.f[0] = fx, d.f[1] = fy, d.i[0] = dw, d.i[1] = dh, d.i[2] = interp;
+  return d;
+}
+
+}  // namespace
+
+VF_EXPORT int vf_resize_out_size(vf_ctx *ctx, int width, int height, int dw, int dh, double fx, double fy, int interp,
+                                 int *out_w, int *out_h) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_resize_out_size";
+  if (!out_w || !out_h) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL result", fn);
+  int rc = check_resize(ctx, fn, dw, dh, fx, fy, interp, 1);
+  if (rc != VF_OK) return rc;
+  if (width == 0 && height == 0) {  // the empty frame stays empty
+    *out_w = *out_h = 0;
+    return VF_OK;
+  }
+  if ((rc = check_frame_shape(ctx, fn, width, height, 1)) != VF_OK) return rc;
+  vf::resize::Plan p;
+  std::string why;
+  if (!vf::resize::frame_ok((uint64_t)width, (uint64_t)height, dw, dh, fx, fy, interp, &p, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  *out_w = p.dw, *out_h = p.dh;
+  return VF_OK;
+}
+
+VF_EXPORT int vf_resize_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels, int dw, int dh,
+                               double fx, double fy, int interp, void *stream) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_resize_device";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_resize(ctx, fn, dw, dh, fx, fy, interp, channels)) != VF_OK) return rc;
+  if (width == 0 && height == 0) return VF_OK;
+  if ((rc = check_frame_shape(ctx, fn, width, height, channels)) != VF_OK) return rc;
+  vf::resize::Plan p;
+  std::string why;
+  if (!vf::resize::frame_ok((uint64_t)width, (uint64_t)height, dw, dh, fx, fy, interp, &p, &why))
+    return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  if (!dsrc || !ddst) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL buffer", fn);
+  const size_t in_bytes = (size_t)width * (size_t)channels * (size_t)height, out_bytes = (size_t)p.dw * (size_t)channels * (size_t)p.dh;
+  const uint8_t *s = (const uint8_t *)dsrc, *d = (const uint8_t *)ddst;
+  if (s < d + out_bytes && d < s + in_bytes)  // out of place only: the two frames are not of one size
+    return set_err(ctx, VF_E_INVALID, 0, "%s: src and dst overlap", fn);
+  VF_HIP(ctx, hipSetDevice(ctx->device));
+  VF_HIP(ctx, vf::launch_resize(dsrc, ddst, width, height, channels, dw, dh, fx, fy, interp, (hipStream_t)stream));
+  return VF_OK;
+}
+
+VF_EXPORT int vf_resize_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts, const int *widths,
+                                    const int *heights, int n, int channels, int dw, int dh, double fx, double fy,
+                                    int interp) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_resize_frames_host";
+  int rc = check_channels(ctx, fn, channels);
+  if (rc != VF_OK) return rc;
+  if ((rc = check_resize(ctx, fn, dw, dh, fx, fy, interp, channels)) != VF_OK) return rc;
+  const ResizeStepData data = resize_step_data(dw, dh, fx, fy, interp);
+  const vf_step step{VF_STEP_RESIZE, 0, 0, 0, &data, 0, 0, 0, 0, 0};  // a program of one step
+  return program_frames_host(ctx, fn, srcs, dsts, widths, heights, n, channels, &step, 1);
+}
+
+// ---- filter chains: a program of table / conv / rank / binary / mix / sep / level / clahe / warp / resize steps on raw frames
 
 namespace {
 
@@ -1258,6 +1399,14 @@ int chain_program(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps,
       std::memcpy(s.warp.m, d.m, sizeof d.m);
       s.warp.mode = d.i[0], s.warp.interp = d.i[1], s.border = in.border;
       for (int c = 0; c < 3; ++c) s.warp.value[c] = (uint8_t)d.i[2 + c];
+    } else if (in.kind == VF_STEP_RESIZE) {
+      // data: two float64 {fx, fy}, then {dw, dh, interp, 0} as int32
+      if (!in.data) return set_err(ctx, VF_E_INVALID, 0, "%s: the resize step's data is NULL", at);
+      ResizeStepData d;
+      std::memcpy(&d, in.data, sizeof d);  // host memory of any alignment
+      if ((rc = check_resize(ctx, at, d.i[0], d.i[1], d.f[0], d.f[1], d.i[2], channels)) != VF_OK) return rc;
+      s.resize.fx = d.f[0], s.resize.fy = d.f[1];
+      s.resize.dw = d.i[0], s.resize.dh = d.i[1], s.resize.interp = d.i[2];
     } else if (in.kind != VF_STEP_BINARY) {
       return set_err(ctx, VF_E_INVALID, 0, "%s: unknown kind %d", at, in.kind);
     }
@@ -1294,6 +1443,26 @@ VF_EXPORT int vf_chain_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint
                                    const int *heights, int n, int channels, const vf_step *steps, int nsteps) {
   VF_CHECK_CTX(ctx);
   return program_frames_host(ctx, "vf_chain_frames_host", srcs, dsts, widths, heights, n, channels, steps, nsteps);
+}
+
+VF_EXPORT int vf_chain_out_size(vf_ctx *ctx, const vf_step *steps, int nsteps, int channels, int width, int height,
+                                int *out_w, int *out_h) {
+  VF_CHECK_CTX(ctx);
+  const char *fn = "vf_chain_out_size";
+  if (!out_w || !out_h) return set_err(ctx, VF_E_INVALID, 0, "%s: NULL result", fn);
+  vf::chain::Program prog;
+  std::vector<uint64_t> masks;
+  int rc = chain_program(ctx, fn, steps, nsteps, channels, &prog, &masks);
+  if (rc != VF_OK) return rc;
+  *out_w = width, *out_h = height;
+  if (width == 0 && height == 0) return VF_OK;  // the empty frame stays empty
+  if ((rc = check_frame_shape(ctx, fn, width, height, channels)) != VF_OK) return rc;
+  if (!vf::chain::has_resize(prog)) return VF_OK;
+  std::vector<vf::chain::Size> sizes;
+  std::string why;
+  if (!vf::chain::value_sizes(prog, width, height, &sizes, &why)) return set_err(ctx, VF_E_INVALID, 0, "%s: %s", fn, why.c_str());
+  *out_w = sizes.back().w, *out_h = sizes.back().h;
+  return VF_OK;
 }
 
 // ---- memory helpers ------------------------------------------------------------------------
@@ -1694,7 +1863,8 @@ int chain_filter(vf_ctx *ctx, const char *fn, const vf_step *steps, int nsteps, 
   if (rc != VF_OK) return rc;
   if (vf::chain::single_kind(spec->prog) == vf::chain::kTable)
     return table_filter(ctx, fn, spec->prog.steps[0].table.data(), spec->prog.steps[0].channels, out);
-  spec->bufs = vf::chain::assign_buffers(spec->prog);
+  // under a resize step the decoded frames keep buffer 0 to themselves (vf_jpeg_host.hip run_filter_encode)
+  spec->bufs = vf::chain::assign_buffers(spec->prog, vf::chain::has_resize(spec->prog));
   out->kind = Filter::kChain;
   out->chain = std::move(spec);
   return VF_OK;
@@ -1748,6 +1918,15 @@ int clahe_filter(vf_ctx *ctx, const char *fn, int clip_q8, int tiles_x, int tile
   if (rc != VF_OK) return rc;
   const int32_t data[4] = {mask, clip_q8, tiles_x, tiles_y};
   const vf_step step{VF_STEP_CLAHE, 0, 0, 0, data, 0, 0, 0, 0, 0};
+  return chain_filter(ctx, fn, &step, 1, out);
+}
+
+// The decoded frames are 3-channel BGR, grayscale inputs included; the encoder takes the result's size.
+int resize_filter(vf_ctx *ctx, const char *fn, int dw, int dh, double fx, double fy, int interp, Filter *out) {
+  const int rc = check_resize(ctx, fn, dw, dh, fx, fy, interp, 3);
+  if (rc != VF_OK) return rc;
+  const ResizeStepData data = resize_step_data(dw, dh, fx, fy, interp);
+  const vf_step step{VF_STEP_RESIZE, 0, 0, 0, &data, 0, 0, 0, 0, 0};
   return chain_filter(ctx, fn, &step, 1, out);
 }
 
@@ -2065,6 +2244,35 @@ VF_EXPORT int vf_jpeg_bench_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const
   Filter filter;
   if (const int rc = warp_filter(ctx, "vf_jpeg_bench_warp", m, mode, interp, border, value, &filter)) return rc;
   return jpeg_filter_bench(ctx, "vf_jpeg_bench_warp", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
+                           filter);
+}
+
+// ---- JPEG with the resize in place of the inversion: the result is encoded at its own size ------------
+
+VF_EXPORT int vf_jpeg_resize(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int dw, int dh,
+                             double fx, double fy, int interp, int quality, int subsamp, int flags, uint8_t *const *outs,
+                             const size_t *caps, size_t *sizes) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = resize_filter(ctx, "vf_jpeg_resize", dw, dh, fx, fy, interp, &filter)) return rc;
+  return jpeg_filter(ctx, "vf_jpeg_resize", jpegs, jpeg_sizes, n, quality, subsamp, flags, outs, caps, sizes, filter);
+}
+
+VF_EXPORT int vf_jpeg_resize_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int dw, int dh,
+                                    double fx, double fy, int interp, int quality, int subsamp, int flags, uint64_t *ticket) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = resize_filter(ctx, "vf_jpeg_resize_submit", dw, dh, fx, fy, interp, &filter)) return rc;
+  return jpeg_filter_submit(ctx, "vf_jpeg_resize_submit", jpegs, jpeg_sizes, n, quality, subsamp, flags, ticket, filter);
+}
+
+VF_EXPORT int vf_jpeg_bench_resize(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n, int dw, int dh,
+                                   double fx, double fy, int interp, int quality, int subsamp, int flags, int iters, float *ms,
+                                   float *stage_ms) {
+  VF_CHECK_CTX(ctx);
+  Filter filter;
+  if (const int rc = resize_filter(ctx, "vf_jpeg_bench_resize", dw, dh, fx, fy, interp, &filter)) return rc;
+  return jpeg_filter_bench(ctx, "vf_jpeg_bench_resize", jpegs, jpeg_sizes, n, quality, subsamp, flags, iters, ms, stage_ms,
                            filter);
 }
 

@@ -10,7 +10,12 @@
 //   * rows      working backwards from an output band, the rows of every value that must exist,
 //               and the program's total vertical reach R;
 //   * launches  per band, every step with its buffers, row offsets and row ranges: the list that
-//               both GPU paths walk and the CPU check simulates.
+//               both GPU paths walk and the CPU check simulates;
+//   * sizes     the width and height of every value: a resize step makes a value of another size
+//               than its operand, every other step one of its operand's size (value_sizes); a
+//               program that holds a resize step is planned on whole frames by frame_launches,
+//               whose launches carry the sizes, and its buffers are as large as the largest value
+//               they hold (buffer_bytes).
 // Every step sees whole-frame borders: a step that makes rows [lo, hi) of its value from an
 // operand of vertical radius r reads the operand's rows [lo - r, hi + r) clipped to the frame, and
 // resolves its border in FRAME coordinates (vf_conv_border.h) exactly as one band of
@@ -26,6 +31,7 @@
 
 #include "vf_clahe_plan.h"
 #include "vf_level_plan.h"
+#include "vf_resize_plan.h"
 #include "vf_warp_plan.h"
 
 namespace vf {
@@ -39,8 +45,9 @@ constexpr int kMaxSepSide = 31;  // the most taps of one axis of a separable ste
 // of this file and of the C ABI have always used for "a kind that does not exist" (refused with
 // "unknown kind 4"), and callers may rely on that refusal, so the colour matrix took 5.  6 and 9
 // are refused in callers' checks the same way, so the separable filter took 7, the level
-// filter 8 and CLAHE 10; 11 stays refused as well, so the warp took 12, and 13 stays refused.
-enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5, kSep = 7, kLevel = 8, kClahe = 10, kWarp = 12 };
+// filter 8 and CLAHE 10; 11 stays refused as well, so the warp took 12, and 13 stays refused, so the
+// resize took 14, and 15 stays refused.
+enum : int { kTable = 0, kConv = 1, kRank = 2, kBinary = 3, kMix = 5, kSep = 7, kLevel = 8, kClahe = 10, kWarp = 12, kResize = 14 };
 enum : int { kRoundHalfEven = 0, kRoundHalfUp = 1 };                             // VF_ROUND_*
 enum : int { kSubtract = 0, kAdd = 1, kAbsdiff = 2, kMin = 3, kMax = 4 };        // VF_BIN_*
 
@@ -59,6 +66,7 @@ struct Step {
   int mask = 0, link = 0, clip_lo = 0, clip_hi = 0;  // kLevel (vf_level_plan.h); mask: kClahe as well
   int clip_q8 = 0, tiles_x = 0, tiles_y = 0;         // kClahe (vf_clahe_plan.h)
   warp::StepData warp = {};                          // kWarp (vf_warp_plan.h); border: kWarp as well
+  resize::StepData resize = {};                      // kResize (vf_resize_plan.h)
 };
 
 struct Program {
@@ -69,17 +77,24 @@ struct Program {
 inline bool is_neighbourhood(const Step &s) { return s.kind == kConv || s.kind == kRank || s.kind == kSep; }
 inline int radius(const Step &s) { return is_neighbourhood(s) ? s.kh / 2 : 0; }  // vertical
 // A step that reads its operand at other places than the one it writes, so never in place: the
-// neighbourhood steps, and a warp step (radius 0: its reach is the whole frame, see whole_frame).
-inline bool reads_elsewhere(const Step &s) { return is_neighbourhood(s) || s.kind == kWarp; }
+// neighbourhood steps, a warp step (radius 0: its reach is the whole frame, see whole_frame) and a
+// resize step, whose result is not even of its operand's size.
+inline bool reads_elsewhere(const Step &s) { return is_neighbourhood(s) || s.kind == kWarp || s.kind == kResize; }
 
 // A level step reads its whole operand before it writes a byte (vf_level.hip), and so does a CLAHE
 // step (vf_clahe.hip: every tile's table is complete before the blend starts): a program that holds
 // one is planned on whole frames only, y0 = 0 and y1 = H, and never cut into bands.  A warp step
-// (vf_warp.hip) reads anywhere in its operand, with the same consequence.
+// (vf_warp.hip) reads anywhere in its operand, with the same consequence, and so does a resize step
+// (vf_resize.hip), whose rows are not its operand's rows.
+inline bool has_resize(const Program &p) {
+  for (const Step &s : p.steps)
+    if (s.kind == kResize) return true;
+  return false;
+}
 inline bool whole_frame(const Program &p) {
   for (const Step &s : p.steps)
     if (s.kind == kLevel || s.kind == kClahe || s.kind == kWarp) return true;
-  return false;
+  return has_resize(p);
 }
 
 // The device scratch of a whole-frame program's steps (run_launches' hist), in bytes: the level
@@ -114,7 +129,7 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
     const Step &s = p.steps[i - 1];
     const std::string at = "step " + std::to_string(i) + ": ";
     if ((s.kind < kTable || s.kind > kBinary) && s.kind != kMix && s.kind != kSep && s.kind != kLevel && s.kind != kClahe &&
-        s.kind != kWarp)
+        s.kind != kWarp && s.kind != kResize)
       return fail(at + "unknown kind " + std::to_string(s.kind));
     if (s.a < 0 || s.a >= i)
       return fail(at + "operand a = " + std::to_string(s.a) + " is not an earlier value");
@@ -145,6 +160,11 @@ inline bool validate(const Program &p, int frame_channels, std::string *why) {
       std::string m;
       const int value[3] = {s.warp.value[0], s.warp.value[1], s.warp.value[2]};
       if (!warp::limits_ok(s.warp.m, s.warp.mode, s.warp.interp, s.border, value, frame_channels, &m)) return fail(at + m);
+    }
+    if (s.kind == kResize) {
+      std::string m;
+      if (!resize::limits_ok(s.resize.dw, s.resize.dh, s.resize.fx, s.resize.fy, s.resize.interp, frame_channels, &m))
+        return fail(at + m);
     }
     if (s.kind == kSep) {
       if (s.kw < 1 || s.kh < 1 || s.kw > kMaxSepSide || s.kh > kMaxSepSide || !(s.kw & 1) || !(s.kh & 1))
@@ -189,7 +209,8 @@ inline void compose_tables(const Step &first, const Step &then, Step *out) {
 // rounding and a clamp between them are not one matrix.  Nor across a separable, a level or a CLAHE
 // step: only table steps are ever composed, and a level or CLAHE step's tables do not exist before
 // the frame does.  Nor across a warp step: a table before one is not a table after one when the
-// constant border's colour enters the blend.
+// constant border's colour enters the blend.  Nor across a resize step: only neighbouring table steps
+// are ever composed, and a table step on each side of one reads and is read by the resize step.
 inline Program fold(const Program &in) {
   Program p = in;
   for (bool again = true; again;) {
@@ -237,7 +258,10 @@ struct Buffers {
 // written; a warp step reads anywhere in its operand: never in place either, reads_elsewhere).  Every
 // value of a buffer sits at one row origin (the band's
 // first source row), so "in place" is dst == operand exactly.
-inline Buffers assign_buffers(const Program &p) {
+// keep_input: buffer 0 holds value 0 and nothing else, ever (the JPEG path under a resize step: the
+// decoded frames lie in buffer 0 at the decoder's offsets, one frame's bytes each, and a later value
+// may be larger than its frame).
+inline Buffers assign_buffers(const Program &p, bool keep_input = false) {
   const int n = p.size();
   std::vector<int> last(n + 1, 0);  // the last step that reads value v; the result outlives all
   for (int i = 1; i <= n; ++i) {
@@ -247,13 +271,14 @@ inline Buffers assign_buffers(const Program &p) {
   last[n] = n + 1;
   Buffers out;
   out.of.assign(n + 1, 0);
-  std::vector<int> holder_dies{last[0]};  // per buffer: the last read of the value it holds
+  std::vector<int> holder_dies{keep_input ? n + 1 : last[0]};  // per buffer: the last read of the value it holds
   for (int i = 1; i <= n; ++i) {
     const Step &s = p.steps[i - 1];
     int pick = -1;
     if (!reads_elsewhere(s)) {  // in place over an operand that dies here
       if (last[s.a] == i) pick = out.of[s.a];
       else if (s.kind == kBinary && last[s.b] == i) pick = out.of[s.b];
+      if (keep_input && pick == 0) pick = -1;
     }
     for (int k = 0; pick < 0 && k < (int)holder_dies.size(); ++k)
       if (holder_dies[k] < i) pick = k;  // its value is dead: no step from i on reads it
@@ -262,7 +287,7 @@ inline Buffers assign_buffers(const Program &p) {
       holder_dies.push_back(0);
     }
     out.of[i] = pick;
-    holder_dies[pick] = last[i];
+    holder_dies[pick] = keep_input && pick == 0 ? n + 1 : last[i];
   }
   out.count = (int)holder_dies.size();
   out.result = out.of[n];
@@ -340,6 +365,8 @@ struct Launch {
   int a_row, b_row, dst_row;  // first row handed to the kernel, relative to s0
   int y0, nrows;              // the rows of this value to make (frame coordinates)
   int src0, nsrc;             // the operand's first row handed over and the count (launch_conv's s0, nsrc)
+  int a_w = 0, a_h = 0;       // frame_launches only: the operand's size (a binary step's two operands agree) ...
+  int w = 0, h = 0;           // ... and the result's; 0 from band_launches: every value has the frame's size
 };
 
 // The launches that make rows [y0, y1) of the result for a frame of H rows whose buffers start at
@@ -358,6 +385,77 @@ inline std::vector<Launch> band_launches(const Program &p, const Buffers &bufs, 
     const bool to_out = result_to_out && i == n;
     out.push_back(Launch{i, bufs.of[s.a], bufs.of[s.kind == kBinary ? s.b : s.a], to_out ? kOut : bufs.of[i], src.lo - s0,
                          r.lo - s0, to_out ? 0 : r.lo - s0, r.lo, r.hi - r.lo, src.lo, src.hi - src.lo});
+  }
+  return out;
+}
+
+// ---- sizes ---------------------------------------------------------------------------------------
+
+struct Size {
+  int w = 0, h = 0;
+};
+
+// The size of every value for a frame of W x H (each at least 1): out[v] for v = 0 .. n.  A resize
+// step makes resize::out_size of its operand's size; every other step a value of its operand's size.
+// false with the reason in *why, naming the step: a resize step that refuses its operand's size
+// (resize::frame_ok), or a binary step whose operands differ in size.
+inline bool value_sizes(const Program &p, int W, int H, std::vector<Size> *out, std::string *why) {
+  const int n = p.size();
+  out->assign((size_t)n + 1, Size{});
+  (*out)[0].w = W, (*out)[0].h = H;
+  for (int i = 1; i <= n; ++i) {
+    const Step &s = p.steps[i - 1];
+    const Size a = (*out)[s.a];
+    const std::string at = "step " + std::to_string(i) + ": ";
+    Size r = a;
+    if (s.kind == kResize) {
+      std::string m;
+      resize::Plan plan;
+      if (!resize::frame_ok((uint64_t)a.w, (uint64_t)a.h, s.resize.dw, s.resize.dh, s.resize.fx, s.resize.fy, s.resize.interp,
+                            &plan, &m)) {
+        if (why) *why = at + m;
+        return false;
+      }
+      r.w = plan.dw, r.h = plan.dh;
+    } else if (s.kind == kBinary) {
+      const Size b = (*out)[s.b];
+      if (a.w != b.w || a.h != b.h) {
+        if (why)
+          *why = at + "operand a (value " + std::to_string(s.a) + ") is " + std::to_string(a.w) + " x " + std::to_string(a.h) +
+                 " and operand b (value " + std::to_string(s.b) + ") is " + std::to_string(b.w) + " x " + std::to_string(b.h) +
+                 ": a binary step's operands have one size";
+        return false;
+      }
+    }
+    (*out)[i] = r;
+  }
+  return true;
+}
+
+// The whole-frame launches of a program whose values have `sizes` (value_sizes): band_launches'
+// list for y0 = 0, y1 = H and s0 = 0, with every row count taken from the value it belongs to and
+// each launch carrying its operand's and its result's size.  For a program without a resize step
+// the first eleven members equal band_launches(p, bufs, H, 0, H, 0, result_to_out)'s.
+inline std::vector<Launch> frame_launches(const Program &p, const Buffers &bufs, const std::vector<Size> &sizes,
+                                          bool result_to_out) {
+  const int n = p.size();
+  std::vector<Launch> out;
+  for (int i = 1; i <= n; ++i) {
+    const Step &s = p.steps[i - 1];
+    const bool to_out = result_to_out && i == n;
+    const Size a = sizes[s.a], r = sizes[i];
+    out.push_back(Launch{i, bufs.of[s.a], bufs.of[s.kind == kBinary ? s.b : s.a], to_out ? kOut : bufs.of[i], 0, 0, 0, 0, r.h, 0,
+                         is_neighbourhood(s) ? a.h : r.h, a.w, a.h, r.w, r.h});
+  }
+  return out;
+}
+
+// The bytes of each buffer: those of the largest value it holds, at `channels` bytes a pixel.
+inline std::vector<size_t> buffer_bytes(const Buffers &bufs, const std::vector<Size> &sizes, int channels) {
+  std::vector<size_t> out((size_t)bufs.count, 0);
+  for (size_t v = 0; v < sizes.size() && v < bufs.of.size(); ++v) {
+    const size_t bytes = (size_t)sizes[v].w * (size_t)sizes[v].h * (size_t)channels;
+    out[(size_t)bufs.of[v]] = std::max(out[(size_t)bufs.of[v]], bytes);
   }
   return out;
 }

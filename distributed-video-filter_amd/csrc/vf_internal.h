@@ -129,13 +129,22 @@ hipError_t launch_clahe(const void *dsrc, void *ddst, int width, int height, int
 hipError_t launch_warp(const void *dsrc, void *ddst, int width, int height, int channels, const double *m, int mode,
                        int interp, int border, const uint8_t *value, hipStream_t stream);
 
+// The resize (vf_resize.hip; cv2.resize) of one frame of width x height pixels of 1 or
+// 3 interleaved channels, packed rows, into a frame of vf_resize_plan.h's out_size: (dw, dh) when
+// they are not 0, rint(width fx) x rint(height fy) otherwise; interp a VF_INTER_* (0 nearest, 1
+// linear, 3 area).  Each frame pointer at any alignment; ddst must not overlap dsrc (the caller
+// checks).  No device memory of its own; asynchronous on `stream`: one launch.
+hipError_t launch_resize(const void *dsrc, void *ddst, int width, int height, int channels, int dw, int dh, double fx,
+                         double fy, int interp, hipStream_t stream);
+
 // The steps of a program as launches of the nine kernels above (vf_api.hip): `launches` is
 // vf_chain_plan.h's band_launches of a band or whole frame, masks[i] step i + 1's element when it
 // is a rank step, bufs[k] the address of buffer k's origin row (the band's row s0), out the rows a
 // chain::kOut launch writes; conv_form as launch_conv's form.  hist: the scratch of the program's
 // level and CLAHE steps, chain::whole_frame_scratch_bytes(prog) bytes laid out as that function
 // says, 16-B aligned device memory that the work queued on `stream` alone uses; NULL when
-// chain::whole_frame(prog) is false.
+// chain::whole_frame(prog) is false.  A launch that carries sizes (chain::frame_launches, for a
+// program with a resize step) gives its step's row pitch and height; w and frame_h hold otherwise.
 namespace chain {
 struct Program;
 struct Launch;

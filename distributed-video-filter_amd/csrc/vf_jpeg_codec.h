@@ -174,6 +174,10 @@ class Codec {
   int run_encode(int bgr, bool fastdct, const uint8_t *pix, std::string *err);
   // what the invert path queues behind its decode: the program, if the batch has one, and the encode
   int run_filter_encode(bool fastdct, std::string *err);
+  // the sizes and pixel offsets the encoder is prepared with: the decoded frames' at their d_pix_ offsets, or,
+  // when the batch's program holds a resize step, each frame's RESULT size (chain::value_sizes of its decoded
+  // size) at an offset of its own in the program's buffers (rz_*_ below)
+  int encode_layout(std::vector<int> *ws, std::vector<int> *hs, std::vector<uint64_t> *offs, std::string *err);
   int queue_fetch(uint64_t guess, std::string *err);
   int finish_fetch(std::string *err);
   int copy_out(uint8_t *const *outs, const size_t *caps, size_t *sizes, std::string *err);
@@ -217,6 +221,11 @@ class Codec {
   DevBuf d_eplanes_;  // the invert path's encoder sample planes (plan_.fuse)
   Filter filter_;  // the batch's filter, set by the entry call before prepare_decode; the stages read it
   DevBuf d_pix2_;  // the convolution's output: the batch's frames at their d_pix_ offsets
+  // a program with a resize step: frame f's values' sizes, and its slot in buffers 1, 2, ... (every value but
+  // the decoded frame, which stays in d_pix_ at F.out_off): rz_offs_[f], the slots rz_bytes_ together
+  std::vector<std::vector<chain::Size>> rz_sizes_;
+  std::vector<uint64_t> rz_offs_;
+  uint64_t rz_bytes_ = 0;
   std::vector<std::unique_ptr<DevBuf>> d_chain_;  // a chain's buffers 2, 3, ...: as d_pix2_ (0 is d_pix_, 1 d_pix2_)
   DevBuf d_level_hist_;  // the scratch of a program's level and CLAHE steps (run_launches' hist): the frames run in order
   int dcm_ = -1;  // k_color layout shared by the batch's frames (1..3, 0 general), -1 mixed

@@ -882,14 +882,40 @@ int Codec::prepare_encode(const int *ws, const int *hs, const uint64_t *img_offs
 // one launch per frame from d_pix_ to d_pix2_ at F.out_off, all rows, form 0.  settle_decode's tails
 // call this, so a batch resynchronised at wait_invert is filtered again from freshly decoded
 // pixels: once.
+int Codec::encode_layout(std::vector<int> *ws, std::vector<int> *hs, std::vector<uint64_t> *offs, std::string *err) {
+  const int n = dn_;
+  ws->resize((size_t)n), hs->resize((size_t)n), offs->resize((size_t)n);
+  const bool sized = filter_.between() && chain::has_resize(filter_.chain->prog);
+  rz_sizes_.clear(), rz_offs_.clear(), rz_bytes_ = 0;
+  for (int f = 0; f < n; ++f) {
+    const DecFrame &F = dfr_[(size_t)f];
+    (*ws)[(size_t)f] = F.g.w, (*hs)[(size_t)f] = F.g.h, (*offs)[(size_t)f] = F.out_off;
+    if (!sized) continue;
+    std::vector<chain::Size> z;
+    std::string why;
+    if (!chain::value_sizes(filter_.chain->prog, F.g.w, F.g.h, &z, &why)) {
+      *err = "frame " + std::to_string(f) + ": " + why;
+      return kInvalid;
+    }
+    uint64_t slot = 0;  // the largest value behind the decoded frame: every such value lives at the one offset
+    for (size_t v = 1; v < z.size(); ++v) slot = std::max(slot, (uint64_t)z[v].w * (uint64_t)z[v].h * 3);
+    (*ws)[(size_t)f] = z.back().w, (*hs)[(size_t)f] = z.back().h, (*offs)[(size_t)f] = rz_bytes_;
+    rz_offs_.push_back(rz_bytes_);
+    rz_bytes_ += align_up(slot + 16, 256);
+    rz_sizes_.push_back(std::move(z));
+  }
+  return kOk;
+}
+
 int Codec::run_filter_encode(bool fastdct, std::string *err) {
   if (!filter_.between()) return run_encode(1, fastdct, d_pix_.as<uint8_t>(), err);
   const ChainSpec &c = *filter_.chain;
+  const bool sized = chain::has_resize(c.prog);  // encode_layout laid the frames out
   while ((int)d_chain_.size() + 2 < c.bufs.count) d_chain_.emplace_back(new DevBuf());
   std::vector<uint8_t *> base((size_t)c.bufs.count), at((size_t)c.bufs.count);
   for (int k = 0; k < c.bufs.count; ++k) {
     DevBuf &b = k == 0 ? d_pix_ : k == 1 ? d_pix2_ : *d_chain_[(size_t)k - 2];
-    if (k != 0) CK(b.ensure(dpix_bytes_));  // d_pix_ holds the decoded frames: sized by prepare_decode
+    if (k != 0) CK(b.ensure(sized ? rz_bytes_ : dpix_bytes_));  // d_pix_ holds the decoded frames: sized by prepare_decode
     base[(size_t)k] = b.as<uint8_t>();
   }
   // a level or CLAHE step's scratch: the frames run in order on s_, so one set a step (a warp step needs none)
@@ -899,7 +925,9 @@ int Codec::run_filter_encode(bool fastdct, std::string *err) {
       if (st.kind != chain::kClahe && st.kind != chain::kWarp) continue;
       for (int f = 0; f < dn_; ++f) {
         std::string why;
-        const uint64_t fw = (uint64_t)dfr_[(size_t)f].g.w, fh = (uint64_t)dfr_[(size_t)f].g.h;
+        // the step's operand: the decoded frame, or under a resize step the value's own size
+        const uint64_t fw = (uint64_t)(sized ? rz_sizes_[(size_t)f][(size_t)st.a].w : dfr_[(size_t)f].g.w),
+                       fh = (uint64_t)(sized ? rz_sizes_[(size_t)f][(size_t)st.a].h : dfr_[(size_t)f].g.h);
         if (st.kind == chain::kClahe ? !clahe::frame_ok(fw, fh, st.tiles_x, st.tiles_y, &why)
                                      : !warp::frame_ok(fw, fh, st.warp.mode, st.warp.m, &why)) {
           *err = "frame " + std::to_string(f) + ": " + why;
@@ -916,6 +944,13 @@ int Codec::run_filter_encode(bool fastdct, std::string *err) {
   for (int f = 0; f < dn_; ++f) {
     const DecFrame &F = dfr_[(size_t)f];
     const int h = F.g.h;
+    if (sized) {  // buffer 0 is the decoded frame alone (assign_buffers' keep_input); the others hold the frame's slot
+      launches = chain::frame_launches(c.prog, c.bufs, rz_sizes_[(size_t)f], false);
+      at[0] = base[0] + F.out_off;
+      for (size_t k = 1; k < base.size(); ++k) at[k] = base[k] + rz_offs_[(size_t)f];
+      CK(run_launches(c.prog, c.masks.data(), launches, at.data(), nullptr, F.g.w, 3, h, 0, hist, cfg, s_));
+      continue;
+    }
     if (h != launches_h) launches = chain::band_launches(c.prog, c.bufs, h, 0, h, 0, false);
     launches_h = h;
     for (size_t k = 0; k < base.size(); ++k) at[k] = base[k] + F.out_off;
@@ -1121,8 +1156,9 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
   const auto t0 = clk::now();
   if ((rc = prepare_decode(jpegs, jsizes, n, flags, sw, err))) return rc;
   const auto t1 = clk::now();
-  std::vector<int> ws((size_t)n), hs((size_t)n);
-  std::vector<uint64_t> offs((size_t)n);
+  std::vector<int> ws, hs;
+  std::vector<uint64_t> offs;
+  if ((rc = encode_layout(&ws, &hs, &offs, err))) return rc;
   // the first D2H copy's size: an inverted frame re-encoded at the input's quality codes to about
   // the input's size (+25 % + 8 KB per frame, the rule before any batch); after the codec's first
   // batch, its measured output/input ratio + 6 % + 1 KB per frame (q95 input re-encoded at q85
@@ -1132,9 +1168,6 @@ int Codec::submit_invert(const uint8_t *const *jpegs, const size_t *jsizes, int 
   uint64_t guess = 0;
   in_bytes_ = 0;
   for (int f = 0; f < n; ++f) {
-    ws[(size_t)f] = dfr_[(size_t)f].g.w;
-    hs[(size_t)f] = dfr_[(size_t)f].g.h;
-    offs[(size_t)f] = dfr_[(size_t)f].out_off;
     in_bytes_ += jsizes[f];
     guess += ratio > 0 ? align_up((uint64_t)((double)jsizes[f] * ratio * 1.06) + 1024, 64)
                        : align_up(jsizes[f] + jsizes[f] / 4 + 8192, 64);
@@ -1263,13 +1296,9 @@ int Codec::bench_invert(const uint8_t *const *jpegs, const size_t *jsizes, int n
   }
   filter_ = filter;
   if ((rc = prepare_decode(jpegs, jsizes, n, flags, JpegSwitches::read(), err))) return rc;
-  std::vector<int> ws((size_t)n), hs((size_t)n);
-  std::vector<uint64_t> offs((size_t)n);
-  for (int f = 0; f < n; ++f) {
-    ws[(size_t)f] = dfr_[(size_t)f].g.w;
-    hs[(size_t)f] = dfr_[(size_t)f].g.h;
-    offs[(size_t)f] = dfr_[(size_t)f].out_off;
-  }
+  std::vector<int> ws, hs;
+  std::vector<uint64_t> offs;
+  if ((rc = encode_layout(&ws, &hs, &offs, err))) return rc;
   const bool fast = plan_.enc_fast;
   if ((rc = prepare_encode(ws.data(), hs.data(), offs.data(), n, quality, subsamp, fast, err))) return rc;
   float acc[8] = {0};

@@ -21,6 +21,7 @@ distributor.py).
                ``clahe`` and ``create_clahe`` (the ``cv2.createCLAHE`` drop-in), ``Clahe`` and ``clahe_frames``
                ``warp_affine``, ``flip`` and ``rotate`` (the ``cv2.warpAffine``, ``cv2.flip`` and ``cv2.rotate(ROTATE_180)``
                drop-ins for frames that keep their size), ``Warp`` and ``warp_frames``
+               ``resize`` (the ``cv2.resize`` drop-in: nearest, linear, area), ``Resize`` and ``resize_frames``
   warps        builders of the usual affine maps (rotation, translation, zoom)
   colors       builders of the usual colour matrices (gray, swap_rb, sepia, saturation, gain, ...)
   kernels      builders of the usual convolution kernels (gaussian3/5/7, sharpen, sobel_x, ...)
@@ -42,6 +43,7 @@ from .filters import Separable, as_taps, blur, box_filter, sep_filter2d, sep_fra
 from .filters import Level, auto_levels, calc_hist, calc_hist_frames, equalize_hist, level_frames  # noqa: F401
 from .filters import Clahe, clahe, clahe_frames, create_clahe  # noqa: F401
 from .filters import Warp, flip, rotate, warp_affine, warp_frames  # noqa: F401
+from .filters import Resize, resize, resize_frames  # noqa: F401
 
 __all__ = [
     "ABI_VERSION", "Context", "VFilterError", "device_count", "get_context", "library_path",
@@ -54,4 +56,5 @@ __all__ = [
     "Level", "equalize_hist", "auto_levels", "calc_hist", "calc_hist_frames", "level_frames",
     "Clahe", "clahe", "create_clahe", "clahe_frames",
     "Warp", "warp_affine", "flip", "rotate", "warp_frames", "warps",
+    "Resize", "resize", "resize_frames",
 ]

@@ -175,6 +175,21 @@ SIGNATURES = {
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
     "vf_jpeg_bench_warp": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p]),
+    "vf_resize_out_size": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_int, _vp, _vp]),
+    "vf_resize_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp]),
+    "vf_resize_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "vf_jpeg_resize": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    "vf_jpeg_resize_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_uint64)]),
+    "vf_jpeg_bench_resize": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, _c_float_p, _c_float_p]),
+    "vf_chain_out_size": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "vf_binary_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
     "vf_chain_frames_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
     "vf_jpeg_chain": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -192,6 +207,8 @@ STEP_LEVEL = 8                                              # VF_STEP_LEVEL: 9 s
 LEVEL_EQUALIZE, LEVEL_STRETCH = 0, 1                        # VF_LEVEL_*
 STEP_CLAHE = 10                                             # VF_STEP_CLAHE: 11 stays refused as well
 STEP_WARP = 12                                              # VF_STEP_WARP: 13 stays refused as well
+STEP_RESIZE = 14                                            # VF_STEP_RESIZE: 15 stays refused as well
+INTER_NEAREST, INTER_LINEAR, INTER_AREA = 0, 1, 3           # VF_INTER_*: cv2's values
 CHAIN_MAX_STEPS = 8                                         # VF_CHAIN_MAX_STEPS
 ROUND_HALF_EVEN, ROUND_HALF_UP = 0, 1                       # VF_ROUND_*
 
@@ -673,6 +690,28 @@ class Context:
         self._check(self._lib.vf_warp_device(self._ctx, dsrc or None, ddst or None, width, height, channels,
                                              *self._warp_args(m, mode, interp, border, value), stream or None))
 
+    # -- the resize (cv2.resize): vf_resize_* ----------------------------------------------------------------
+    def resize_out_size(self, width: int, height: int, dw: int = 0, dh: int = 0, fx: float = 0.0, fy: float = 0.0,
+                        interp: int = INTER_LINEAR) -> tuple:
+        """``(width, height)`` of the result for a frame of ``width`` x ``height``."""
+        ow, oh = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self._lib.vf_resize_out_size(self._ctx, width, height, int(dw), int(dh), float(fx), float(fy),
+                                                 int(interp), ctypes.byref(ow), ctypes.byref(oh)))
+        return ow.value, oh.value
+
+    def resize_frames_host(self, srcs: Sequence, dsts: Sequence, widths: Sequence[int], heights: Sequence[int],
+                           channels: int, dw: int = 0, dh: int = 0, fx: float = 0.0, fy: float = 0.0,
+                           interp: int = INTER_LINEAR) -> None:
+        """``dsts[i]`` holds frame i's result size (``resize_out_size``)."""
+        sa, da, wa, ha, n = self._frame_arrays(srcs, dsts, widths, heights)
+        self._check(self._lib.vf_resize_frames_host(self._ctx, sa, da, wa, ha, n, channels, int(dw), int(dh), float(fx),
+                                                    float(fy), int(interp)))
+
+    def resize_device(self, dsrc: int, ddst: int, width: int, height: int, channels: int, dw: int = 0, dh: int = 0,
+                      fx: float = 0.0, fy: float = 0.0, interp: int = INTER_LINEAR, stream: int = 0) -> None:
+        self._check(self._lib.vf_resize_device(self._ctx, dsrc or None, ddst or None, width, height, channels, int(dw),
+                                               int(dh), float(fx), float(fy), int(interp), stream or None))
+
     # -- filter chains (vf_chain_*, vf_binary_device) ------------------------------------------------
     def _steps(self, steps: Sequence):
         """``steps`` -- ``filters.Chain.args[0]``: tuples ``(kind, a, b, op, data, shift, border)`` with
@@ -711,6 +750,10 @@ class Context:
                 d = np.frombuffer(np.array([float(v) for v in m], np.float64).tobytes() + ints.tobytes(), np.uint8)
                 if d.shape != (72,):
                     raise ValueError("a warp step's data is (the six entries of m, mode, interp, the three border bytes)")
+            elif kind == STEP_RESIZE:  # data: (dw, dh, fx, fy, interp) -> two float64, then four int32
+                dw, dh, fx, fy, interp = data
+                ints = np.array([int(dw), int(dh), int(interp), 0], np.int32)
+                d = np.frombuffer(np.array([float(fx), float(fy)], np.float64).tobytes() + ints.tobytes(), np.uint8)
             else:
                 d = None
             if d is not None:
@@ -724,6 +767,15 @@ class Context:
         arr, keep = self._steps(steps)
         self._check(self._lib.vf_chain_frames_host(self._ctx, sa, da, wa, ha, n, channels, arr, len(steps)))
         del keep
+
+    def chain_out_size(self, steps: Sequence, channels: int, width: int, height: int) -> tuple:
+        """``(width, height)`` of the program's result for a frame of ``width`` x ``height``."""
+        arr, keep = self._steps(steps)
+        ow, oh = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self._lib.vf_chain_out_size(self._ctx, arr, len(steps), channels, width, height, ctypes.byref(ow),
+                                                ctypes.byref(oh)))
+        del keep
+        return ow.value, oh.value
 
     def binary_device(self, da: int, db: int, ddst: int, nbytes: int, op: int, stream: int = 0) -> None:
         """``ddst[i] = op(da[i], db[i])`` over device memory, ``op`` a ``VF_BIN_*``; asynchronous."""
@@ -1299,6 +1351,38 @@ class Context:
         """``jpeg_warp_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
         return self._jpeg_submit("jpeg_warp_submit_addrs", self._lib.vf_jpeg_warp_submit,
                                  self._warp_args(m, mode, interp, border, value), addrs, sizes, quality, subsamp, flags)
+
+    # -- JPEG with the resize in place of the inversion (vf_jpeg_resize*); tickets are invert tickets ---------
+    @staticmethod
+    def _resize_args(dw, dh, fx, fy, interp) -> tuple:
+        """``filters.Resize.args`` as the C arguments."""
+        return int(dw), int(dh), float(fx), float(fy), int(interp)
+
+    def jpeg_resize(self, jpegs: Sequence, dw: int, dh: int, fx: float, fy: float, interp: int, quality: int, subsamp: int,
+                    flags: int = 0) -> list:
+        """decode -> resize -> encode for every JPEG on the GPU; returns bytes, each of its result's size."""
+        if len(jpegs) == 0:
+            return []
+        ticket = self.jpeg_resize_submit(jpegs, dw, dh, fx, fy, interp, quality, subsamp, flags)
+        return [v.tobytes() for v in self.jpeg_invert_result(ticket)]
+
+    def jpeg_resize_submit(self, jpegs: Sequence, dw: int, dh: int, fx: float, fy: float, interp: int, quality: int,
+                           subsamp: int, flags: int = 0) -> int:
+        """``jpeg_invert_submit`` with the resize; collect with the ``jpeg_invert_result*`` methods."""
+        return self._jpeg_submit("jpeg_resize_submit", self._lib.vf_jpeg_resize_submit,
+                                 self._resize_args(dw, dh, fx, fy, interp), jpegs, None, quality, subsamp, flags)
+
+    def jpeg_resize_submit_addrs(self, addrs: np.ndarray, sizes: np.ndarray, dw: int, dh: int, fx: float, fy: float,
+                                 interp: int, quality: int, subsamp: int, flags: int = 0) -> int:
+        """``jpeg_resize_submit`` from address / size arrays (the JPEGs in a worker's ring slots)."""
+        return self._jpeg_submit("jpeg_resize_submit_addrs", self._lib.vf_jpeg_resize_submit,
+                                 self._resize_args(dw, dh, fx, fy, interp), addrs, sizes, quality, subsamp, flags)
+
+    def jpeg_bench_resize(self, jpegs: Sequence, dw: int, dh: int, fx: float, fy: float, interp: int, quality: int,
+                          subsamp: int, flags: int = 0, iters: int = 10):
+        """``jpeg_bench_invert`` with the resize between the decode and the encode."""
+        return self._jpeg_bench(self._lib.vf_jpeg_bench_resize, self._resize_args(dw, dh, fx, fy, interp), "color",
+                                jpegs, quality, subsamp, flags, iters)
 
     def jpeg_bench_warp(self, jpegs: Sequence, m, mode: int, interp: int, border: int, value, quality: int,
                         subsamp: int, flags: int = 0, iters: int = 10):

@@ -1242,6 +1242,141 @@ def warp_frames(frames: Sequence, f: Warp, outs: Optional[List] = None, ctx: Opt
                         lambda *a: (ctx or get_context()).warp_frames_host(*a, *f.args))
 
 
+# -- the resize: cv2.resize -------------------------------------------------------------------------
+
+RESIZE_INTERPOLATIONS = {"nearest": 0, "linear": 1, "area": 3}  # VF_INTER_*: cv2's INTER_NEAREST, INTER_LINEAR, INTER_AREA
+RESIZE_MAX_SIDE = 32767
+
+
+def _resize_interp(interpolation) -> int:
+    if isinstance(interpolation, str) and interpolation in RESIZE_INTERPOLATIONS:
+        return RESIZE_INTERPOLATIONS[interpolation]
+    if isinstance(interpolation, (int, np.integer)) and not isinstance(interpolation, (bool, np.bool_)):
+        if int(interpolation) in (2, 4):
+            raise ValueError(f"Resize: interpolation {int(interpolation)} (cv2's INTER_CUBIC 2, INTER_LANCZOS4 4) is not "
+                             "built; \"nearest\" 0, \"linear\" 1 and \"area\" 3 are")
+        if int(interpolation) in RESIZE_INTERPOLATIONS.values():
+            return int(interpolation)
+    raise ValueError(f"Resize: interpolation must be one of {sorted(RESIZE_INTERPOLATIONS)} (or cv2's 0, 1, 3), "
+                     f"not {interpolation!r}")
+
+
+@dataclasses.dataclass(frozen=True, init=False, eq=False)
+class Resize:
+    """``cv2.resize(src, dsize, fx=fx, fy=fy, interpolation=...)`` on uint8 frames of 1 or 3 channels: ``dsize`` is
+    ``(width, height)``, or it is ``None`` (or ``(0, 0)``) and ``fx``, ``fy`` scale every frame's own size to
+    ``rint(W fx) x rint(H fy)``, half to even, so one value resizes frames of mixed sizes.  ``interpolation``
+    "nearest", "linear" or "area" (or cv2's 0, 1, 3); area is built for integer shrink factors of 1 to 16 (another
+    scale is refused for the frame that has it), and linear at exactly 2 x 2 runs as area, as in cv2.  The first
+    filter value whose result has another size than its operand: ``out_size(w, h)`` says which.  Bit-exact by
+    the rule of DESIGN.md 26."""
+    dsize: Optional[tuple]  # (width, height); None: by fx, fy
+    fx: float
+    fy: float
+    interpolation: str
+    interp_code: int
+    family = "resize"
+
+    def __init__(self, dsize=None, fx=0, fy=0, interpolation="linear"):
+        code = _resize_interp(interpolation)
+        if dsize is not None:
+            try:
+                d = tuple(dsize)
+                ok = len(d) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in d)
+            except TypeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"Resize: dsize is (width, height) integers or None, not {dsize!r}")
+            d = (int(d[0]), int(d[1]))
+            if d == (0, 0):
+                d = None  # cv2's empty Size(): by fx, fy
+            elif not all(1 <= v <= RESIZE_MAX_SIDE for v in d):
+                raise ValueError(f"Resize: dsize = {dsize!r}; a side is 1 to {RESIZE_MAX_SIDE}")
+            dsize = d
+        try:
+            fx, fy = float(fx), float(fy)
+        except (TypeError, ValueError):
+            raise ValueError(f"Resize: fx and fy are numbers, not {fx!r}, {fy!r}") from None
+        if dsize is None and not (np.isfinite(fx) and np.isfinite(fy) and fx > 0 and fy > 0):
+            raise ValueError(f"Resize: without dsize, fx and fy are finite and positive, not {fx!r}, {fy!r}")
+        name = {v: k for k, v in RESIZE_INTERPOLATIONS.items()}[code]
+        for k, v in (("dsize", dsize), ("fx", fx), ("fy", fy), ("interpolation", name), ("interp_code", code)):
+            object.__setattr__(self, k, v)
+
+    @property
+    def args(self) -> tuple:
+        """``(dw, dh, fx, fy, interp)``: the C arguments, and a VF_STEP_RESIZE step's data."""
+        dw, dh = self.dsize if self.dsize is not None else (0, 0)
+        return dw, dh, self.fx, self.fy, self.interp_code
+
+    def out_size(self, w: int, h: int) -> tuple:
+        """``(width, height)`` of the result for a frame of ``w`` x ``h`` (vf_resize_plan.h's out_size)."""
+        w, h = int(w), int(h)
+        if not (1 <= w <= RESIZE_MAX_SIDE and 1 <= h <= RESIZE_MAX_SIDE):
+            raise ValueError(f"Resize: a frame of {w} x {h}; a side is 1 to {RESIZE_MAX_SIDE}")
+        if self.dsize is not None:
+            return self.dsize
+        out = tuple(int(min(max(np.rint(np.float64(n) * np.float64(f)), -2.0 ** 31), 2.0 ** 31 - 1)) for n, f in ((w, self.fx), (h, self.fy)))
+        if min(out) < 1:
+            raise ValueError(f"Resize: a frame of {w} x {h} resizes to {out[0]} x {out[1]}: a side of 0")
+        if max(out) > RESIZE_MAX_SIDE:
+            raise ValueError(f"Resize: a frame of {w} x {h} resizes to {out[0]} x {out[1]}; a side is at most {RESIZE_MAX_SIDE}")
+        return out
+
+
+def _sized_dst(name: str, src: np.ndarray, size: tuple, dst) -> np.ndarray:
+    """``dst`` made or checked for a result of ``size`` = (width, height) and ``src``'s channels."""
+    shape = (size[1], size[0]) + src.shape[2:]
+    if dst is None:
+        return np.empty(shape, np.uint8)
+    if not isinstance(dst, np.ndarray) or dst.shape != shape or dst.dtype != np.uint8 or not dst.flags.c_contiguous:
+        raise ValueError(f"{name}: dst must be a C-contiguous uint8 array of the result's shape {shape}, not "
+                         f"{getattr(dst, 'shape', type(dst).__name__)}")
+    return dst
+
+
+def _sized_frames_call(name: str, srcs: List[np.ndarray], outs: Optional[List], out_size, call) -> List:
+    """``_frames_call`` where frame i's result has ``out_size(width, height)``."""
+    srcs = [np.ascontiguousarray(s) for s in srcs]
+    chans = {1 if s.ndim == 2 else s.shape[2] for s in srcs}
+    if len(chans) > 1:
+        raise ValueError(f"{name}: the frames of one call have one channel count")
+    if outs is not None and len(outs) != len(srcs):
+        raise ValueError(f"{name}: outs must hold one array a frame")
+    outs = [(np.empty_like(s) if outs is None else o) if not s.size
+            else _sized_dst(name, s, out_size(s.shape[1], s.shape[0]), None if outs is None else o)
+            for s, o in zip(srcs, outs if outs is not None else [None] * len(srcs))]
+    live = [(s, o) for s, o in zip(srcs, outs) if s.size]
+    if live:
+        call([s for s, _ in live], [o for _, o in live], [s.shape[1] for s, _ in live],
+             [s.shape[0] for s, _ in live], chans.pop())
+    return outs
+
+
+def resize(src: np.ndarray, dsize=None, fx=0, fy=0, interpolation="linear", dst: Optional[np.ndarray] = None,
+           ctx: Optional[Context] = None) -> np.ndarray:
+    """Drop-in for ``cv2.resize(src, dsize, fx=fx, fy=fy, interpolation=...)`` on uint8 ``H x W`` or ``H x W x 3``
+    input (``Resize`` has the arguments).  ``dst``, when given, has the result's shape; it may not share memory with
+    ``src`` unless the two sizes are equal."""
+    f = Resize(dsize, fx, fy, interpolation)
+    src = np.ascontiguousarray(_conv_frame("resize", src))
+    if not src.size:
+        return _rank_dst("resize", src, dst)
+    dst = _sized_dst("resize", src, f.out_size(src.shape[1], src.shape[0]), dst)
+    channels = 1 if src.ndim == 2 else src.shape[2]
+    (ctx or get_context()).resize_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, *f.args)
+    return dst
+
+
+def resize_frames(frames: Sequence, f: Resize, outs: Optional[List] = None, ctx: Optional[Context] = None) -> List:
+    """A ``Resize`` over separately stored frames of one channel count and mixed sizes in one call.  Returns ndarrays
+    (or fills ``outs``, C-contiguous arrays of the results' shapes)."""
+    if not isinstance(f, Resize):
+        raise ValueError("resize_frames: the filter is a Resize")
+    return _sized_frames_call("resize_frames", [_conv_frame("resize_frames", a) for a in frames], outs, f.out_size,
+                              lambda *a: (ctx or get_context()).resize_frames_host(*a, *f.args))
+
+
 # -- filter chains: a program of filters between one upload and one download ----------------------
 
 STEP_TABLE, STEP_CONV, STEP_RANK, STEP_BINARY = 0, 1, 2, 3  # VF_STEP_* (include/vfilter.h)
@@ -1250,6 +1385,7 @@ STEP_SEP = 7  # VF_STEP_SEP: 6 stays refused as well
 STEP_LEVEL = 8  # VF_STEP_LEVEL: 9 stays refused as well
 STEP_CLAHE = 10  # VF_STEP_CLAHE: 11 stays refused as well
 STEP_WARP = 12  # VF_STEP_WARP: 13 stays refused as well
+STEP_RESIZE = 14  # VF_STEP_RESIZE: 15 stays refused as well
 BINARY_OPS = {"subtract": 0, "add": 1, "absdiff": 2, "min": 3, "max": 4}  # VF_BIN_*
 CHAIN_MAX_STEPS = 8  # VF_CHAIN_MAX_STEPS
 MORPH_OPS = ("erode", "dilate", "open", "close", "gradient", "tophat", "blackhat")
@@ -1299,6 +1435,8 @@ def _unary_step(f, a: int) -> tuple:
         return (STEP_CLAHE, a, 0, 0, (f.mask, f.clip_q8, f.tiles_x, f.tiles_y), 0, 0)
     if isinstance(f, Warp):
         return (STEP_WARP, a, 0, 0, (f.m if f.m is not None else (0.0,) * 6, f.mode, f.interp_code, f.value), 0, f.border_code)
+    if isinstance(f, Resize):
+        return (STEP_RESIZE, a, 0, 0, f.args, 0, 0)
     # existing callers match the list up to "not <type>" word for word, so a newer filter value is named after it
     raise ValueError("chain: a step is Invert, Table, Kernel, Rank, Mix, Separable, Level, Combine or Chain, or a Clahe, "
                      f"not {type(f).__name__} (a Warp is a step as well)")
@@ -1389,11 +1527,35 @@ class Chain:
         """3 when a level step names channel 1 or 2 (such a chain takes 3-channel frames only), else 1."""
         return 3 if any(st[0] in (STEP_LEVEL, STEP_CLAHE) and st[4][0] >> 1 for st in self.steps) else 1
 
+    @property
+    def has_resize(self) -> bool:
+        """True when a step is a ``Resize``: the result's size is ``out_size``'s, not the frame's."""
+        return any(st[0] == STEP_RESIZE for st in self.steps)
+
+    def out_size(self, w: int, h: int) -> tuple:
+        """``(width, height)`` of the result for a frame of ``w`` x ``h``: a ``Resize`` step makes a value of another
+        size, every other step one of its operand's.  ``ValueError`` for a two-input step whose operands differ in
+        size, naming the step.  Pure Python on purpose: ``chain`` and ``chain_frames`` allocate results with it
+        before a GPU context exists, and a ``Chain`` is built and sized on machines without one;
+        ``Context.chain_out_size`` is the library's own answer (csrc/vf_chain_plan.h ``value_sizes``), and the GPU
+        tests hold the two equal, refusals included."""
+        sizes = [(int(w), int(h))]
+        for i, (kind, a, b, _op, data, _shift, _border) in enumerate(self.steps, 1):
+            size = sizes[a]
+            if kind == STEP_RESIZE:
+                dw, dh, fx, fy, interp = data
+                size = Resize((dw, dh) if dw or dh else None, fx, fy, interp).out_size(*size)
+            elif kind == STEP_BINARY and sizes[b] != size:
+                raise ValueError(f"chain: step {i}: operand a (value {a}) is {size[0]} x {size[1]} and operand b (value {b}) "
+                                 f"is {sizes[b][0]} x {sizes[b][1]}: a binary step's operands have one size")
+            sizes.append(size)
+        return sizes[-1]
+
     def __len__(self) -> int:
         return len(self.steps)
 
 
-_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable, Level, Clahe, Warp)
+_CHAIN_ITEMS = (Invert, Table, Kernel, Rank, Mix, Separable, Level, Clahe, Warp, Resize)
 
 
 def _lower(item, cur: int, prog: List[tuple]) -> int:
@@ -1469,7 +1631,10 @@ def chain(src: np.ndarray, steps, dst: Optional[np.ndarray] = None, ctx: Optiona
     with one upload and one download.  ``dst`` as for ``filter2d``, and it may be ``src``."""
     c = _as_chain(steps)
     src = np.ascontiguousarray(_chain_frame("chain", src, c))
-    dst = _rank_dst("chain", src, dst)
+    if c.has_resize and src.size:  # the result has Chain.out_size's size; a dst of another shape is refused
+        dst = _sized_dst("chain", src, c.out_size(src.shape[1], src.shape[0]), dst)
+    else:
+        dst = _rank_dst("chain", src, dst)
     channels = 1 if src.ndim == 2 else src.shape[2]
     if src.size:
         (ctx or get_context()).chain_frames_host([src], [dst], [src.shape[1]], [src.shape[0]], channels, *c.args)
@@ -1480,6 +1645,9 @@ def chain_frames(frames: Sequence, chain, outs: Optional[List] = None, ctx: Opti
     """A ``Chain`` over separately stored frames of one channel count and mixed sizes in one call.
     Returns ndarrays (or fills ``outs``, C-contiguous arrays of the frames' shapes)."""
     c = _as_chain(chain)
+    if c.has_resize:
+        return _sized_frames_call("chain_frames", [_chain_frame("chain_frames", f, c) for f in frames], outs, c.out_size,
+                                  lambda *a: (ctx or get_context()).chain_frames_host(*a, *c.args))
     return _frames_call("chain_frames", [_chain_frame("chain_frames", f, c) for f in frames], outs,
                         lambda *a: (ctx or get_context()).chain_frames_host(*a, *c.args))
 

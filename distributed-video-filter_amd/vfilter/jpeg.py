@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import Context, get_context, jpeg_header
-from .filters import Clahe, Invert, Kernel, Level, Morph, Rank, Separable, Table, Warp, _as_chain, _as_mix, _warp_flags
+from .filters import Clahe, Invert, Kernel, Level, Morph, Rank, Resize, Separable, Table, Warp, _as_chain, _as_mix, _warp_flags
 
 # TurboJPEG constants (turbojpeg.h / PyTurboJPEG)
 TJPF_RGB, TJPF_BGR = 0, 1
@@ -300,6 +300,18 @@ class TurboJPEG:
         if isinstance(code, (int, np.integer)) and not isinstance(code, (bool, np.bool_)):
             code = 1 if code > 0 else -1 if code < 0 else 0
         return self.filter_batch([jpeg_buf], Warp(flip=code, interpolation="nearest"), quality, jpeg_subsample, flags)[0]
+
+    # -- the resize (cv2.resize): the result is a JPEG of another size ------------------------------------
+    def resize(self, jpeg_buf, dsize=None, fx=0, fy=0, interpolation="linear", quality: int = 85,
+               jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:
+        """``encode(vfilter.resize(decode(jpeg_buf), dsize, fx, fy, interpolation))`` on the GPU, the pixels never
+        leaving it; the JPEG's header carries the result's size."""
+        return self.filter_batch([jpeg_buf], Resize(dsize, fx, fy, interpolation), quality, jpeg_subsample, flags)[0]
+
+    def resize_batch(self, jpeg_bufs: Sequence, dsize=None, fx=0, fy=0, interpolation="linear", quality: int = 85,
+                     jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> List[bytes]:
+        """``resize`` over a batch of mixed input sizes in one GPU pass; with ``fx``, ``fy`` each from its own size."""
+        return self.filter_batch(jpeg_bufs, Resize(dsize, fx, fy, interpolation), quality, jpeg_subsample, flags)
 
     # -- a filter chain (vfilter.filters.Chain) between one decode and one encode ------------------------
     def chain(self, jpeg_buf, chain, quality: int = 85, jpeg_subsample: int = TJSAMP_422, flags: int = 0) -> bytes:

@@ -704,6 +704,67 @@ int vf_jpeg_bench_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
                        const double *m, int mode, int interp, int border, const int *value,
                        int quality, int subsamp, int flags, int iters, float *ms, float *stage_ms);
 
+/* ---- the resize (cv2.resize) --------------------------------------------------------------------
+ * A uint8 frame of W x H pixels of 1 or 3 interleaved channels becomes one of dw x dh: with dw and
+ * dh not 0 that size, scale_x = 1.0 / ((double)dw / W); with both 0 and fx, fy finite and positive
+ * dw = rint(W fx) (half to even), scale_x = 1.0 / fx, which is not W / dw.  The same in y.  Every
+ * double and float operation is rounded separately, none fused (written from OpenCV
+ * 3.x .. 4.10 resize.cpp's generic path, bit-exact by the rule below, which governs).
+ *   VF_INTER_NEAREST  sx(dx) = min(floor(dx scale_x), W - 1), the same in y; dst = src[sy][sx].
+ *   VF_INTER_LINEAR   per column f = (float)((dx + 0.5) scale_x - 0.5), sx = floor(f), f -= sx; sx < 0:
+ *                     f = 0, sx = 0; sx >= W - 1: f = 0, sx = W - 1; a0 = rint((1.f - f) 2048.f), a1 =
+ *                     rint(f 2048.f); the taps are columns sx and min(sx + 1, W - 1).  Per row the same
+ *                     without the two resets: rows clamp(sy, 0, H - 1) and clamp(sy + 1, 0, H - 1) with
+ *                     b0, b1 as they are.  In int32, h(r) = (S[r][sx] a0 + S[r][sx1] a1) >> 4 and
+ *                     dst = (((b0 h(r0)) >> 16) + ((b1 h(r1)) >> 16) + 2) >> 2.
+ *   VF_INTER_AREA     iscale_x = rint(scale_x); built where |scale_x - iscale_x| < DBL_EPSILON on both
+ *                     axes and both factors are 1 .. 16: dst is the mean of the iscale_x x iscale_y
+ *                     block at (dx iscale_x, dy iscale_y), (sum + 2) >> 2 at 2 x 2, else
+ *                     sat(rint((float)sum * (1.f / (iscale_x iscale_y)))).  A block that overruns the
+ *                     frame (the fx, fy form only: columns dx >= W / iscale_x, and every column of a
+ *                     row block past H) is sat(rint((float)sum / count)) over its pixels inside.
+ * Linear with both factors exactly 2 runs as area, as in cv2.  Limits, VF_E_INVALID with the reason
+ * before any GPU work: sides of source and result 1 .. 32767; area at any other scale; cubic (2) and
+ * Lanczos (4) are not built.  The empty frame is a no-op. */
+#define VF_INTER_NEAREST 0
+#define VF_INTER_LINEAR  1
+#define VF_INTER_AREA    3
+
+/* The size of the result for a frame of width x height.  No GPU work. */
+int vf_resize_out_size(vf_ctx *ctx, int width, int height, int dw, int dh, double fx, double fy,
+                       int interp, int *out_w, int *out_h);
+
+/* Enqueue the filter on `stream` over one device-resident frame; ddst holds the result's size
+ * (ask the function above): any alignment; ddst must not overlap dsrc at all; returns after the launch. */
+int vf_resize_device(vf_ctx *ctx, const void *dsrc, void *ddst, int width, int height, int channels,
+                     int dw, int dh, double fx, double fy, int interp, void *stream);
+
+/* The filter on `n` separately allocated host frames of mixed sizes and one channel count,
+ * synchronous; dsts[i] holds frame i's result size, and must not overlap srcs[i] unless the two
+ * sizes are equal.  A frame or a result that does not fit the context's staging whole is refused:
+ * a frame is never cut into bands. */
+int vf_resize_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
+                          const int *widths, const int *heights, int n, int channels, int dw,
+                          int dh, double fx, double fy, int interp);
+
+/* vf_jpeg_invert with the filter in place of the inversion: decode -> resize -> encode on the GPU,
+ * on the decoded 3-channel BGR frame (grayscale inputs included).  Every output JPEG has its
+ * frame's RESULT size (header, MCU padding and block counts follow it); a batch may mix input
+ * sizes, and with fx, fy each frame is scaled from its own size. */
+int vf_jpeg_resize(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                   int dw, int dh, double fx, double fy, int interp, int quality, int subsamp,
+                   int flags, uint8_t *const *outs, const size_t *caps, size_t *sizes);
+
+/* vf_jpeg_invert_submit with the filter.  The ticket is an invert ticket. */
+int vf_jpeg_resize_submit(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes,
+                          int n, int dw, int dh, double fx, double fy, int interp, int quality,
+                          int subsamp, int flags, uint64_t *ticket);
+
+/* vf_jpeg_bench_invert with the filter between the decode and the encode. */
+int vf_jpeg_bench_resize(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
+                         int dw, int dh, double fx, double fy, int interp, int quality,
+                         int subsamp, int flags, int iters, float *ms, float *stage_ms);
+
 /* ---- filter chains (cv2.morphologyEx, difference of blurs, ...) -----------------------------
  * A program is a straight-line list of 1 .. VF_CHAIN_MAX_STEPS steps over values.
  * Value 0 is the input frame (uint8, 1 or 3 interleaved channels, packed rows), value i the result
@@ -729,6 +790,11 @@ int vf_jpeg_bench_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
  *   VF_STEP_WARP    the affine warp: `data` six float64 m, then six int32 {mode, interp, value B,
  *                   G, R, 0} (48 + 24 bytes), with `border`.  It reads anywhere in its operand: the
  *                   same refusal, and it never runs in place
+ *   VF_STEP_RESIZE  the resize: `data` two float64 {fx, fy}, then four int32 {dw, dh, interp, 0}
+ *                   (16 + 16 bytes).  Its value has another size than its operand; every other
+ *                   step makes a value of its operand's size, and a binary step whose operands
+ *                   differ in size is refused per frame, naming the step.  The same refusal of a
+ *                   frame, or of any value, that does not fit the staging whole; never in place
  * `data` is a HOST pointer, read during the call only.  VF_E_INVALID, before any GPU work: a step
  * that reads a later value or itself, a value other than the last that no step reads, a 3-channel
  * table or a colour matrix on 1-channel frames, more than VF_CHAIN_MAX_STEPS steps, and anything
@@ -736,7 +802,7 @@ int vf_jpeg_bench_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
  * The VF_STEP_* values are not dense: 4 names no kind and stays refused ("unknown kind 4"), as
  * callers' checks of the refusal expect, so VF_STEP_MIX is 5; 6 likewise, so VF_STEP_SEP is 7 and
  * VF_STEP_LEVEL 8; 9 stays refused too, so VF_STEP_CLAHE is 10; 11 stays refused, so
- * VF_STEP_WARP is 12, and 13 stays refused. */
+ * VF_STEP_WARP is 12; 13 stays refused, so VF_STEP_RESIZE is 14, and 15 stays refused. */
 #define VF_STEP_TABLE  0
 #define VF_STEP_CONV   1
 #define VF_STEP_RANK   2
@@ -746,6 +812,7 @@ int vf_jpeg_bench_warp(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *j
 #define VF_STEP_LEVEL  8
 #define VF_STEP_CLAHE  10
 #define VF_STEP_WARP   12
+#define VF_STEP_RESIZE 14
 #define VF_BIN_SUBTRACT 0
 #define VF_BIN_ADD      1
 #define VF_BIN_ABSDIFF  2
@@ -758,8 +825,8 @@ typedef struct vf_step {
   int a, b;         /* operand values; b for VF_STEP_BINARY only */
   int op;           /* VF_STEP_RANK: a VF_RANK_*; VF_STEP_BINARY: a VF_BIN_*; VF_STEP_MIX, VF_STEP_SEP: a VF_ROUND_*; VF_STEP_LEVEL: a VF_LEVEL_* */
   const void *data; /* the table, the int16 weights, the element or the int32 of a matrix, of
-                       separable taps, of a level step or of a CLAHE step, or a warp step's
-                       doubles and int32 (host memory) */
+                       separable taps, of a level step or of a CLAHE step, or a warp or resize
+                       step's doubles and int32 (host memory) */
   int kw, kh;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP */
   int shift;        /* VF_STEP_CONV, VF_STEP_MIX, VF_STEP_SEP */
   int border;       /* VF_STEP_CONV, VF_STEP_RANK, VF_STEP_SEP, VF_STEP_WARP: a VF_BORDER_* */
@@ -778,14 +845,22 @@ int vf_binary_device(vf_ctx *ctx, const void *da, const void *db, void *ddst, si
  * than the context's staging is cut into bands of rows with the program's total vertical reach R
  * (the largest summed radius along a path) as halo; VF_E_INVALID when 2 R + 1 rows of a frame do
  * not fit it.  Intermediate values live in device scratch of the context, allocated by the first
- * call that needs them and freed with the context. */
+ * call that needs them and freed with the context.  dsts[i] holds frame i's RESULT, whose size is
+ * the frame's unless the program holds a resize step (the function below says it); then srcs[i]
+ * and dsts[i] may be equal or overlap only where the two sizes are equal. */
 int vf_chain_frames_host(vf_ctx *ctx, const uint8_t *const *srcs, uint8_t *const *dsts,
                          const int *widths, const int *heights, int n, int channels,
                          const vf_step *steps, int nsteps);
 
+/* The size of the program's result for a frame of width x height, with every check that
+ * vf_chain_frames_host makes of the steps and of the sizes of the values.  No GPU work. */
+int vf_chain_out_size(vf_ctx *ctx, const vf_step *steps, int nsteps, int channels, int width,
+                      int height, int *out_w, int *out_h);
+
 /* vf_jpeg_invert with the program in place of the inversion: decode -> the steps -> encode on
  * the GPU with one decode and one encode, on the decoded BGR frame (3 channels).  A program that
- * folds to a single table runs in the fused colour stage, as vf_jpeg_lut does. */
+ * folds to a single table runs in the fused colour stage, as vf_jpeg_lut does.  A program with a
+ * resize step is encoded at its result's size, frame by frame. */
 int vf_jpeg_chain(vf_ctx *ctx, const uint8_t *const *jpegs, const size_t *jpeg_sizes, int n,
                   const vf_step *steps, int nsteps, int quality, int subsamp, int flags,
                   uint8_t *const *outs, const size_t *caps, size_t *sizes);
